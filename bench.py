@@ -19,11 +19,18 @@ accessions -> 20M + 20M + 10M).  `value` keeps the contract's definition -- inpu
 region starts: for every slab in turn the slab is regenerated on the device (untimed, a stand-in for loading it),
 then exactly K scoring steps of that slab are timed between barriers; the timed regions of all slabs (and of the
 final certificate / gather / likelihood, and of the second pass over the slabs for flagged accessions) add up to K
-steps of the whole job.  The job INCLUDING regeneration is timed once more and reported as `end_to_end`.
+steps of the whole job.  With --full the job INCLUDING regeneration is timed once more and reported as `end_to_end`.
 
 Values P(-1,0,1,2) ~ (0.05,0.60,0.33,0.02) from a counter-based RNG generated on the device; sample = planted
 accession 417 with 2 % error, 80 % PL-derived weights, generated on the device as well (numpy twins in
 snpmatch_amd.synth check both in the tests).
+
+A plain run does only what the headline needs: set up, warm up, the K timed steps, the result line.  --full adds what
+is measured beside it: the CPU baselines and the GPU-vs-CPU count check, the job once more including the slab
+regeneration (`end_to_end`), the read-only kernel's ceiling, and the child legs (packed panel, real-panel
+configurations, DB staging).  --dump-outputs DIR writes what the last timed step computed (per-accession score,
+ninfo, likelihood, LRT in accession order) as DIR/<name>.npy in float64; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -285,6 +292,40 @@ def join_library_group(args, ctx, dev, rank, world, n_acc, shards, use_dist, sid
     return group, coll, join_s
 
 
+DUMP_MAX_ACC = 1 << 20          # accessions per dumped array: at most 5 arrays x 8 MB
+
+
+def dump_outputs(out_dir, shards, lik, lrt, gathered_by_group, n_acc, rank, side_group):
+    """What the last timed step left behind, as a caller of the path receives it: score (fp64 totals), ninfo (informative
+    sites), lik and lrt per accession in accession order -> out_dir/<name>.npy, float64.  Every rank hands its shard's
+    totals to rank 0 (over the gloo side group), rank 0 writes.  A job of more than DUMP_MAX_ACC accessions keeps a fixed
+    seeded sample of them, named in accession.npy."""
+    import torch
+    torch.cuda.synchronize()
+    mine = (shards.score_loc[:shards.n_local].cpu().numpy(), shards.ninfo_loc[:shards.n_local].cpu().numpy())
+    parts = [mine]
+    if side_group is not None:
+        import torch.distributed as dist
+        parts = [None] * shards.world
+        dist.all_gather_object(parts, mine, group=side_group)
+    if rank != 0:
+        return
+    if gathered_by_group:           # the library's all-gather leaves the full vectors in accession order
+        lik_h, lrt_h = lik[:n_acc].cpu().numpy(), lrt[:n_acc].cpu().numpy()
+    else:
+        lik_h, lrt_h = shards.unpad(lik), shards.unpad(lrt)
+    arrays = {"score": np.concatenate([p[0] for p in parts]), "ninfo": np.concatenate([p[1] for p in parts]),
+              "lik": lik_h, "lrt": lrt_h}
+    if n_acc > DUMP_MAX_ACC:
+        idx = np.sort(np.random.default_rng(SEED).choice(n_acc, DUMP_MAX_ACC, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["accession"] = idx
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert len(a) == min(n_acc, DUMP_MAX_ACC), (name, a.shape)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -316,6 +357,12 @@ def main():
     ap.add_argument("--collective", default="c-abi", choices=["c-abi", "torch"],
                     help="who runs the all-gather of the per-accession results at N>1: the library itself (snpm_group_*: RCCL "
                          "communicator inside libsnpmatch_hip.so, one packed all-gather) or torch.distributed")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: CPU baselines and the count check against them, the "
+                         "end-to-end pass with slab regeneration, the read-only kernel's ceiling, the child legs (packed panel, "
+                         "real-panel configurations, DB staging); the --no-* options above drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-accession results of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     # Contract: ONE JSON line on stdout.  RCCL prints a version banner to stdout when its first communicator
@@ -333,7 +380,7 @@ def main():
         args.gpus = world
 
     numpy_all_cores = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         try:
             numpy_all_cores = cpu_baseline_numpy_all_cores(args.n_acc)       # before anything touches the GPU (fork)
         except Exception as e:          # noqa: BLE001
@@ -541,9 +588,12 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         ranks_agree = bool(int(lo.item()) == int(hi.item()))
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shards, lik, lrt, group is not None, n_acc, rank, side_group)
+
     # ---- the job once more INCLUDING the regeneration of every slab (what a panel larger than HBM really costs)
     end_to_end = None
-    if S > 1 and not args.no_end_to_end:
+    if args.full and S > 1 and not args.no_end_to_end:
         c2 = engine.Carry(ctx, n_loc)
         barrier()
         t0 = time.perf_counter()
@@ -598,7 +648,7 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         # rank 0 at every N: the reference's CPU path on a bounded sample of ITS shard, and the counts of the GPU
         # path on the same rows against it (the other ranks wait at the barrier below)
         load_slab(0)
@@ -616,7 +666,7 @@ def main():
     # what a kernel that only READS this slab reaches on this GPU (k_calib_read: 4 B per lane, non-temporal, no
     # arithmetic): the practical ceiling next to the 8 TB/s of the data sheet
     ceiling = None
-    if rank == 0:
+    if args.full and rank == 0:
         ts = []
         for i in range(5):
             t0 = time.perf_counter()
@@ -648,7 +698,7 @@ def main():
                             % (workload_name(n_acc, n_snp), n_acc, n_snp, "2-bit packed" if args.packed else "int8", world, n_loc, n_snp,
                                n_snp * panel.pitch / 1e9, S, "+".join(str(s) for s in slabs), rows_per_slab * panel.pitch / 1e9),
                 "n_acc": n_acc, "n_snp": n_snp, "acc_per_gpu": n_loc, "mode": args.mode, "chunk": chunk,
-                "panel_format": "packed2" if args.packed else "int8", "slabs": slabs,
+                "panel_format": "packed2" if args.packed else "int8", "slabs": slabs, "full": args.full,
                 "sample": "planted accession %d, 2%% error, %s (generated on the device)"
                           % (planted, "hard 0/1 calls" if args.hard_calls else "80% PL weights"),
                 "parallelism": "acc-shard x%d + all-gather (%s)" % (world, coll["transport"]),
@@ -688,7 +738,8 @@ def main():
         dist.destroy_process_group()
     ctx.close()
     if rank == 0:
-        child_legs(out, args, world)
+        if args.full:
+            child_legs(out, args, world)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

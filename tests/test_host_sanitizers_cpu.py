@@ -5,11 +5,23 @@ with a small driver (tests/host_asan_driver.cpp) and run on the reference's samp
 intersection inputs.  GPU sanitizers are not available on the pool; the device code is covered by the parity tests.
 """
 import os
+import platform
+import shutil
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "snpmatch_amd", "csrc")
+# a library the environment preloads may come before the ASan runtime; ASan copes as long as it does not replace malloc
+ASAN_LINK_ORDER = "verify_asan_link_order=0"
+
+
+def tsan_cmd(cmd):
+    """GCC's ThreadSanitizer expects the program's PIE image where the kernel puts it with default address-space
+    randomisation; kernels with more mmap entropy place it elsewhere ("unexpected memory mapping").  The driver runs with
+    randomisation off for its own process (setarch -R), which puts every mapping where TSan expects it."""
+    setarch = shutil.which("setarch")
+    return [setarch, platform.machine(), "-R"] + cmd if setarch else cmd
 
 
 def test_host_sources_under_asan_and_ubsan(tmp_path, golden_dir):
@@ -20,8 +32,7 @@ def test_host_sources_under_asan_and_ubsan(tmp_path, golden_dir):
     subprocess.check_call(cmd)
     work = tmp_path / "cases"
     work.mkdir()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    env.pop("LD_PRELOAD", None)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:" + ASAN_LINK_ORDER, UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe, os.path.join(golden_dir, "701_501.filter.vcf.gz"), str(work)], capture_output=True, text=True,
                        env=env, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
@@ -60,8 +71,7 @@ def test_pooled_intersection_under_tsan(tmp_path):
                            "-I", os.path.join(ROOT, "include"), "-I", CSRC, os.path.join(ROOT, "tests", "intersect_tsan_driver.cpp"),
                            os.path.join(CSRC, "snpm_host.cpp"), "-o", exe])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
-    env.pop("LD_PRELOAD", None)
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run(tsan_cmd([exe]), capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
     assert r.stdout.strip().endswith("done") and "fails=0" in r.stdout
@@ -92,8 +102,8 @@ def test_hdf5_reader_under_asan_and_ubsan(tmp_path, golden_dir):
         p = str(tmp_path / ("damaged_%03d.hdf5" % k))
         open(p, "wb").write(bytes(raw))
         bad.append(p)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:allocator_may_return_null=1", UBSAN_OPTIONS="print_stacktrace=1")
-    env.pop("LD_PRELOAD", None)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:allocator_may_return_null=1:" + ASAN_LINK_ORDER,
+               UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe] + good + bad, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
@@ -116,10 +126,10 @@ def test_loader_building_blocks_under_tsan_and_asan(tmp_path):
                               ["-I", CSRC, src, "-o", exe])
         work = tmp_path / name
         work.mkdir()
-        env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=1",
+        env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=1:" + ASAN_LINK_ORDER,
                    UBSAN_OPTIONS="print_stacktrace=1")
-        env.pop("LD_PRELOAD", None)
-        r = subprocess.run([exe, str(work)], capture_output=True, text=True, env=env, timeout=900)
+        cmd = [exe, str(work)]
+        r = subprocess.run(tsan_cmd(cmd) if name == "tsan" else cmd, capture_output=True, text=True, env=env, timeout=900)
         assert r.returncode == 0, (name, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
         assert "ThreadSanitizer" not in r.stderr and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
         assert "fails=0" in r.stdout and r.stdout.strip().endswith("done")

@@ -5,7 +5,7 @@ resident, one 200k-SNP sample: the GATHERED access shape of Genotyper.genotyper,
 batch of 64 samples whose inputs already are in HBM, and configs[2] (the 399 windows of `snpmatch cross` at 300 kb,
 core/csmatch.py:80-95) -- on the int8 panel and on the 2-bit packed panel (the drop-in classes' default residency).
 
-bench.py runs this as a child process after the headline job and puts the JSON it prints under "real_panel"; run alone
+bench.py --full runs this as a child process after the headline job and puts the JSON it prints under "real_panel"; run alone
 (optionally under rocprofv3) it is the workload of the profiles/r04_real_panel_* summaries.
 
 Per leg: the scoring kernel's name, its average duration from HIP events on the library's stream (snpm_profile_*), the

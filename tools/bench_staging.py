@@ -13,7 +13,7 @@ hipMemcpyAsync on a side stream"; it replaces the h5py read of the reference, co
   and what the rates mean for the one-time load of configs[3] (10 000 x 50M int8 = 500 GB of DB bytes).
 
 Rates are int8 DB bytes per second (rows x accessions / time): what the reference's g.g.snps[idx, :] would have to deliver.
-bench.py runs this as a child process and puts the JSON it prints under "staging".
+bench.py --full runs this as a child process and puts the JSON it prints under "staging".
 
 usage: tools/bench_staging.py [--gb 20] [--h5-gb 4] [--shm-dir /dev/shm] [--threads 16]
 """

@@ -6,7 +6,7 @@ out=gpurun_out/r02; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 step() { echo "== $*"; }
 step "default bench (N=1: whole 10k x 50M job in slabs)"
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $out/bench_n1.json 2> $out/bench_n1.err; echo "rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $out/bench_n1.json 2> $out/bench_n1.err; echo "rc=$?"
 step "per-GPU shapes of N=2,4,8 on one GPU"
 for na in 5000 2500 1252; do
   timeout -k 10 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --n-acc $na > $out/bench_shape_${na}x50M.json 2> $out/bench_shape_${na}.err; echo "$na rc=$?"

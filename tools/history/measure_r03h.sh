@@ -13,5 +13,5 @@ for shape in "10000 50000000" "8192 50000000" "16384 30000000" "6144 40000000"; 
   set -- $shape
   timeout -k 10 300 python bench.py --packed --n-acc $1 --n-snp $2 --mode fast --steps 6 --warmup 2 --no-cpu-baseline --no-alternatives --no-end-to-end 2>/dev/null | line packed-PL $1 $2
 done | tee $out/wide_packed_nospill.txt
-timeout -k 10 600 python bench.py --no-cpu-baseline > $out/bench_default_nospill.json 2>$out/bench_default_nospill.err
+timeout -k 10 600 python bench.py --full --no-cpu-baseline > $out/bench_default_nospill.json 2>$out/bench_default_nospill.err
 tail -c 1500 $out/bench_default_nospill.json

@@ -9,7 +9,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   echo "== gpu tests"; timeout -k 10 700 python -m pytest tests -x -q -m gpu > $out/gpu_tests.log 2>&1; echo "rc=$?"; tail -2 $out/gpu_tests.log
 fi
 echo "== smoke"; timeout -k 10 300 python __graft_entry__.py smoke > $out/smoke.log 2>&1; echo "rc=$?"
-echo "== default bench"; timeout -k 10 500 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "rc=$?"
+echo "== default bench"; timeout -k 10 500 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "rc=$?"
 echo "== rocprofv3 kernel trace of the same job"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end --no-alternatives --no-real-panel > $out/bench_under_rocprof.json 2> $out/prof_bench.err; echo "rc=$?"
 python tools/kernel_trace_by_shape.py --phase-marker k_synth $out/prof_bench > $out/bench_kernel_by_shape.csv

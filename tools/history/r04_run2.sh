@@ -3,7 +3,7 @@ set -uo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r04f; mkdir -p $out
 timeout -k 10 600 python -m pytest tests -x -q -m gpu > $out/gpu_tests.log 2>&1; echo "gpu tests rc=$?"; tail -3 $out/gpu_tests.log
-timeout -k 10 400 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
 timeout -k 10 200 python bench.py --force-dist --n-snp 6250000 --steps 5 --warmup 1 --no-cpu-baseline > $out/bench_force_dist.json 2> $out/bench_force_dist.err; echo "force-dist rc=$?"
 SNPM_BENCH_SIMULATE_STUCK_JOIN=0 timeout -k 10 200 python bench.py --force-dist --group-timeout 5 --n-snp 6250000 --steps 5 --warmup 1 --no-cpu-baseline > $out/bench_stuck_join.json 2> $out/bench_stuck_join.err; echo "stuck-join rc=$? (3 expected)"
 python - <<'PY'

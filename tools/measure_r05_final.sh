@@ -12,7 +12,7 @@ PARTS=${PARTS:-"tests smoke bench prof pmc panel shared once shards strict confi
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has tests; then echo "== gpu tests"; timeout -k 10 900 python -m pytest tests -q -m gpu > $out/gpu_tests.log 2>&1; echo "rc=$?"; tail -2 $out/gpu_tests.log; fi
 if has smoke; then echo "== smoke"; timeout -k 10 300 python __graft_entry__.py smoke > $out/smoke.log 2>&1; echo "rc=$?"; tail -1 $out/smoke.log; fi
-if has bench; then echo "== default bench"; timeout -k 10 700 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "rc=$?"; fi
+if has bench; then echo "== default bench"; timeout -k 10 700 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "rc=$?"; fi
 if has prof; then
   echo "== rocprofv3 kernel trace of the same job"
   timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end --no-alternatives --no-real-panel --no-staging > $out/bench_under_rocprof.json 2> $out/prof_bench.err; echo "rc=$?"
