@@ -160,8 +160,12 @@ static int shared_rows_try(snpm_ctx *ctx, SegJob &j, bool forced, SharedStats &s
     // the int32 accumulators of a tile hold sums of digits (|d| <= 128) over its rows
     if (steps_per_tile * SH_STEP_ROWS > (int64_t(1) << 23) && ctx->shared_force_tiles <= 0) { st.reason = 7; return SNPM_OK; }
     if (ctx->shared_force_tiles > 0) {
-        n_tiles = (int)std::min<int64_t>(ctx->shared_force_tiles, n_steps);
-        steps_per_tile = ((n_steps + n_tiles - 1) / n_tiles + SH_DEPTH - 1) / SH_DEPTH * SH_DEPTH;
+        // a forced count is raised as far as that bound needs: a tile of more rows wraps its sums silently
+        int64_t want = std::min<int64_t>(ctx->shared_force_tiles, n_steps);
+        for (;; ++want) {
+            steps_per_tile = ((n_steps + want - 1) / want + SH_DEPTH - 1) / SH_DEPTH * SH_DEPTH;
+            if (steps_per_tile * SH_STEP_ROWS <= (int64_t(1) << 23)) break;
+        }
         n_tiles = (int)((n_steps + steps_per_tile - 1) / steps_per_tile);
     }
     const int64_t samples_per_pass = std::max<int64_t>(1, groups_per_pass * SH_GROUP_ROWS / rps);

@@ -350,13 +350,15 @@ k_sh_expand(const uint32_t *__restrict__ pos, int64_t ld_pos, const double *__re
             const double *wr = w + 3 * (int64_t)(e[i] ? e[i] - 1 : 0);
             wv[i][0] = wr[0]; wv[i][1] = wr[2]; wv[i][2] = wr[1];              // class order: ref, alt, het
         }
-        // the weights are vetted where they are read: outside [0, 1] (or not finite) -> the whole batch goes back to the per-sample
-        // pass (meta[1] bit 1, read by the host with the results); a weight that is not an integer -> the sample's reference-order
-        // bound is not zero
+        // the weights are vetted where they are read: outside [0, 1] (or not finite; the het weight under skip_hets: not finite)
+        // -> the whole batch goes back to the per-sample pass (meta[1] bit 1, read by the host with the results), which reports a
+        // non-finite one; a weight that is not an integer -> the sample's reference-order bound is not zero
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int ul = i * 256 + (int)threadIdx.x;
             uint32_t lo[3], hi[3];
+            // a het weight that skip_hets leaves unscored must still be finite (the per-sample pass refuses it in any column)
+            if (e[i] && skip_hets && !(fabs(wv[i][2]) <= 1.7976931348623157e308)) out_of_range = true;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 double x = (c == 2 && skip_hets) ? 0.0 : wv[i][c];
@@ -709,12 +711,18 @@ k_sh_finish(const int *__restrict__ partial, int n_tiles, int n_groups, int64_t 
     score[sg * ldo + a] = v;
     ninfo[sg * ldo + a] = informative;
     if (nonint) {
-        const double E = sh_eseg_of(len, chunk, nonint[sg]) + 8.0 * 1.1102230246251565e-16 * (fabs(v) + 1.0);
-        // quantisation, one-sided: every matched SNP may lose up to 2^-F (counted for all of them: an upward-only slack cannot
-        // flag an exact-integer score, floor(v) = floor(v + Eq) as long as Eq < 1)
-        const double Eq = __builtin_ldexp((double)len, -frac_bits) * 1.0000001;
-        const double lo_v = v - E, hi_v = (v + Eq) + E;
-        if (!(lo_v >= 0.0) || floor(lo_v) != floor(hi_v) || a < force_first) {
+        // a sample whose weights are all 0 or 1 has no error to certify: those weights quantise exactly (Q = 0 or 2^F), the digit
+        // sums are exact integers, and v (their hi / lo conversion, an integer below 2^53) is the reference's score itself
+        bool unproven = false;
+        if (nonint[sg]) {
+            const double E = sh_eseg_of(len, chunk, 1) + 8.0 * 1.1102230246251565e-16 * (fabs(v) + 1.0);
+            // quantisation, one-sided: every matched SNP may lose up to 2^-F (counted for all of them: an upward-only slack cannot
+            // flag an exact-integer score, floor(v) = floor(v + Eq) as long as Eq < 1)
+            const double Eq = __builtin_ldexp((double)len, -frac_bits) * 1.0000001;
+            const double lo_v = v - E, hi_v = (v + Eq) + E;
+            unproven = !(lo_v >= 0.0) || floor(lo_v) != floor(hi_v);
+        }
+        if (unproven || a < force_first) {
             const int k = atomicAdd(count, 1);
             if (k < cap) {
                 pairs[2 * k] = (int32_t)sg;

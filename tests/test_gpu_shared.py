@@ -4,6 +4,7 @@ contraction of fixed-point weight digits with the one-hot panel (snpmatch_amd/cs
 reference-order re-evaluation as the per-sample pass.  Reference: one `Genotyper.genotyper` run per sample over the same
 panel (core/snpmatch.py:207-233, the chunk loop :218-225); counts and informative sites must be bit-equal to the C oracle
 and to the per-sample pass, for overlapping and disjoint marker sets, int8 and packed panels.
+The quoted shapes, the automatic 6-digit rule, hard-call batches and the int32 tile bound: tests/test_gpu_shared_scale.py.
 """
 import os
 
@@ -124,9 +125,43 @@ def test_fewer_digits_flag_more_pairs_and_stay_exact(digits):
     st = engine.batch_last_stats(ctx)
     assert st["taken"] and st["digits"] == digits and st["row_tiles"] >= 2, st
     check_against_oracle(db, samples, got, False, digits=digits)
+    # the pairs the certificate flags, bracketed by a model of the fixed-point sums: every pair whose interval [v, v + len 2^-F]
+    # holds an integer (with a margin either way far above the reference-order bound, ~1e-9 here); samples of 0 / 1 weights none
+    lower = upper = 0
+    for rows, wei in samples:
+        if np.all((wei == 0.0) | (wei == 1.0)):
+            continue
+        v = fixed_point_sums(db, rows, wei, digits)
+        eq = len(rows) * 2.0 ** -(8 * (digits - 1) + 6)
+        lower += int(np.sum((v + eq - 1e-8 > v + 1e-8) & (np.floor(v + 1e-8) != np.floor(v + eq - 1e-8))))
+        upper += int(np.sum(np.floor(v - 1e-8) != np.floor(v + eq + 1e-8)))
+    assert lower <= got["pairs_reeval"] <= upper and not got["strict_fallback"], (lower, got["pairs_reeval"], upper)
     if digits == 3:
-        assert got["pairs_reeval"] > 100 or got["strict_fallback"]          # 2^-22 per SNP: hundreds of unproven pairs
+        assert lower > 0                                                    # 2^-22 per SNP: the quantisation alone leaves pairs unproven
+        # the same batch with 7 digits (2^-54 per SNP): fewer pairs flagged, the same counts
+        engine.batch_configure(ctx, shared_rows=1, digits=7)
+        fine = engine.score_batch(panel, samples, 1000, False, engine.MODE_EXACT)
+        assert engine.batch_last_stats(ctx)["digits"] == 7
+        assert fine["pairs_reeval"] < got["pairs_reeval"], (fine["pairs_reeval"], got["pairs_reeval"])
+        assert np.array_equal(fine["ninfo"], got["ninfo"]) and np.array_equal(fine["score"].astype(np.int64), got["score"].astype(np.int64))
     ctx.close()
+
+
+def fixed_point_sums(db, rows, wei, digits):
+    """what the contraction computes for one sample before its certificate: per accession the sum over its rows of
+    Q = floor(w 2^F) of the weight of the accession's call, times 2^-F (exact on the device; here as two int64 halves, good to
+    1e-15 relative)"""
+    F = 8 * (digits - 1) + 6
+    q = np.floor(np.asarray(wei) * 2.0 ** F)
+    hi = np.floor(q / 2.0 ** 27)
+    lo = (q - hi * 2.0 ** 27).astype(np.int64)
+    hi = hi.astype(np.int64)
+    calls = db[rows]
+    v = np.zeros(db.shape[1])
+    for code, col in ((0, 0), (1, 2), (2, 1)):                             # ref, alt, het calls score W[:, 0], W[:, 2], W[:, 1]
+        m = (calls == code).astype(np.int64)
+        v += (m.T @ hi[:, col]) * 2.0 ** (27 - F) + (m.T @ lo[:, col]) * 2.0 ** -F
+    return v
 
 
 @pytest.mark.parametrize("packed", [False, True])
