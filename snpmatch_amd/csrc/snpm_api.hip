@@ -65,9 +65,6 @@ struct snpm_ctx {
     Buf ws_part_score, ws_part_miss, ws_seg_score, ws_seg_miss, ws_seg_off, ws_cols, ws_tmp_score, ws_tmp_ninfo, ws_flags;
     Buf ws_lik_y, ws_lik_n, ws_lik_l, ws_lik_r;
     Buf ws_wprops, ws_epart;            // partial sums of k_wprops / k_eref
-    Buf ws_tickets;                     // k_reduce_all: one ticket per column block, zero between launches
-    int even_tiles = 1;                 // SNPM_EVEN_TILES=0: short int8 queries keep 128-row tiles (round 4) instead of tiles that divide evenly over the parts
-    int fused_reduce = 0;               // SNPM_FUSED_REDUCE=1: k_reduce_groups + k_reduce as ONE launch with a ticket per column block (measured SLOWER: 12.8 us against 5.4 + 4.7 us on a 200k-SNP sample, profiles/r05_once_timeline.txt)
     int once_tail = 1;                  // SNPM_ONCE_TAIL=0: snpm_genotype_once ends with k_scan_few + k_once_finish instead of k_once_tail
     Buf ws_once, ws_once_table;         // packed results of snpm_genotype_once; the weight table of its coded form
     std::vector<double> once_table;     // host image of ws_once_table
@@ -76,7 +73,6 @@ struct snpm_ctx {
     Buf ws_once_state;                  // {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls
     bool once_state_clean = false;
     int once_fused = 1;                 // SNPM_ONCE_FUSED=0: snpm_genotype_once keeps the unfused kernels and copies of its first version
-    int once_zero_copy = 1;             // SNPM_ONCE_ZEROCOPY=0: the fused form sends the slab through the copy engine (two pieces behind the fill) instead of reading it in place
     Buf ws_seg_desc, ws_eseg, ws_pairs, ws_pair_sums, ws_bscore, ws_bninfo, ws_bout, ws_blut, ws_brows, ws_brows32, ws_bw, ws_bcodes;   // segmented / batched scoring
     // shared-row scan of a batch (snpm_api_shared.hpp): union of the samples' rows, the int8 digit matrix, partial digit sums
     Buf ws_sh_bitmap, ws_sh_wordbase, ws_sh_blocks, ws_sh_urows, ws_sh_meta, ws_sh_A, ws_sh_pos, ws_sh_partial;
@@ -87,13 +83,6 @@ struct snpm_ctx {
     double shared_min_density = -1.0;   // auto threshold; negative: by panel format (shared_min_density_of)
     size_t shared_ws_bytes = size_t(2) << 30;   // SNPM_SHARED_WS_MB: digit matrix per pass over groups of samples
     int shared_force_tiles = 0;         // SNPM_SHARED_TILES: row tiles of k_sh_mfma (tests, experiments)
-    int shared_fill = 1;                // SNPM_SHARED_FILL=0: no filler tiles on the CUs the XCD-aligned row tiles leave idle
-    int shared_probe = 1;               // SNPM_SHARED_PROBE=0: the automatic policy decides after the full pass over the batch only
-    int shared_parts = 1;               // SNPM_SHARED_PARTS=n: the pass in n parts, the digit layout of a part (auxiliary stream) beside the previous part's contraction.
-                                        // Measured SLOWER (64 x 200k x 1135: 1.08 ms on one stream, 1.28 / 1.33 / 1.91 ms with 2 / 4 / 8 parts: the layout's waves take issue slots
-                                        // and L1 from the one-wave-per-SIMD contraction, and a part no longer fills the chip), kept for experiments
-    hipStream_t aux_stream = nullptr;   // created with the context
-    hipEvent_t aux_ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -132,26 +121,13 @@ struct snpm_ctx {
     size_t ev_used = 0;
     std::vector<std::pair<size_t, size_t>> prof_pairs[PK_COUNT];
     // tunables (environment)
-    int force_bpl = 0;
-    int force_wpb = 0;
-    int seg_blocks_per_cu = 0;          // SNPM_SEG_BLOCKS_PER_CU: parts of a segmented pass per CU and column block (0: 32 on int8 panels, 8 on packed ones)
-    int part_min_tiles = 8;             // SNPM_PART_MIN_TILES: tiles a part keeps when k_fast_packed_q4 takes more parts than resident blocks
-    int q4_tile_rows = 0;               // SNPM_Q4_TILE_ROWS: rows per LDS tile of k_fast_packed_q4 (0: by block size)
-    int parts_mult = 1;
     int use_acc_major = 1;  // keep an accession-major packed copy (+25 % memory) for contiguous re-evaluation reads
     int64_t acc_major_min_rows = 1000000;   // ... once a query is long enough for the strided path to hurt
-    int strict4 = 1;           // dense strict scoring with 4 columns per lane (SNPM_STRICT4=0: one column per lane)
     int debug_max_parts = 0;   // SNPM_DEBUG_MAX_PARTS=k: cap the parts of the fast pass (tests of multi-epoch parts)
     int packed_split = 1;   // SNPM_PACKED_SPLIT=0: packed panels keep whole rows at a 256-B pitch (round 3's layout)
     int debug_reeval = 0;   // SNPM_DEBUG_REEVAL=k: also re-evaluate accessions 0..k-1 (to time that path)
     int stage_threads = 8;  // host threads filling the pinned staging slabs (default: the cores of this process, at most 16)
-    int nt_loads = 1;      // panel bytes are read once: non-temporal loads (+5-8% measured)
     int64_t f1_slab_bytes = int64_t(2) << 30;   // SNPM_F1_SLAB_BYTES: compacted-weight scratch of the in-silico crosses
-    int occ_cap = 0;          // SNPM_OCC_CAP=n: at most n resident blocks per CU in the fast pass (experiments)
-    int full_occupancy = 0;   // SNPM_FULL_OCCUPANCY=1: as many resident blocks as the occupancy API allows
-    int bits_path = 1;     // SNPM_BITS=0: hard-call samples on packed panels go through k_fast_packed_q4 like any other
-    int64_t pitch_align = 256;          // SNPM_PITCH_ALIGN: bytes a panel row is padded to (a multiple of 64; experiments)
-    bool pitch_align_forced = false;    // set by SNPM_PITCH_ALIGN: no per-width choice
     int64_t long_scan_rows = 2000000;   // SNPM_LONG_SCAN_ROWS: queries of at least this many rows walk LONG_TILE_ROWS-row tiles (int8 fast pass); -1: never
     // live panels of this context: snpm_destroy releases their device memory and orphans them (and their
     // queries), so that a panel / query handle freed AFTER its context is a harmless host-side delete
@@ -165,7 +141,7 @@ struct snpm_panel {
     int64_t n_snp = 0, n_acc = 0;
     int64_t n_acc_total = 0;            // accessions of the panel the REFERENCE would see (= n_acc unless this is one shard of a wider
                                         // panel, snpm_panel_set_total_accessions): 1 selects numpy's vector summation (k_strict_single)
-    int64_t pitch = 0;                  // bytes per SNP row (int8: >= n_acc; packed: >= n_acc / 4), multiple of ctx->pitch_align (256)
+    int64_t pitch = 0;                  // bytes per SNP row (int8: >= n_acc; packed: >= n_acc / 4), multiple of 256 (128 where that saves 5 % of an int8 row)
                                         // -- or, for a SPLIT packed panel, main part + tail part (e.g. 256 + 32): what a row costs in HBM
     int64_t kpitch = 0;                 // what the kernels stride rows by: pitch, or the main part's pitch (a multiple of 256, may be 0)
     int64_t tail_pitch = 0, tail_off = 0;   // split packed panels: bytes per row of the tail matrix / its offset from d (else 0)
@@ -477,55 +453,20 @@ try {
         return set_err(nullptr, SNPM_ERR_HIP, "hipStreamCreate failed");
     }
     ctx->stream = ctx->own_stream;
-    // auxiliary compute stream + its events (the shared-row scan lays out a part's digits beside the previous part's contraction);
-    // without them that pass simply runs on one stream
-    if (hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->aux_stream = nullptr;
-    } else {
-        for (auto &ev : ctx->aux_ev)
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                (void)hipStreamDestroy(ctx->aux_stream);
-                ctx->aux_stream = nullptr;
-                break;
-            }
-    }
-    if (const char *s = getenv("SNPM_FORCE_BPL")) ctx->force_bpl = atoi(s);
-    if (const char *s = getenv("SNPM_PARTS_MULT")) ctx->parts_mult = std::max(1, atoi(s));
-    if (const char *s = getenv("SNPM_FORCE_WPB")) ctx->force_wpb = atoi(s);
-    if (const char *s = getenv("SNPM_Q4_TILE_ROWS")) ctx->q4_tile_rows = atoi(s);
-    if (const char *s = getenv("SNPM_PART_MIN_TILES")) ctx->part_min_tiles = std::max(1, atoi(s));
-    if (const char *s = getenv("SNPM_SEG_BLOCKS_PER_CU")) ctx->seg_blocks_per_cu = std::max(1, atoi(s));
-    if (const char *s = getenv("SNPM_NT")) ctx->nt_loads = atoi(s);
-    if (const char *s = getenv("SNPM_BITS")) ctx->bits_path = atoi(s);
-    if (const char *s = getenv("SNPM_PITCH_ALIGN")) {
-        ctx->pitch_align = std::max<int64_t>(64, (atoll(s) + 63) / 64 * 64);
-        ctx->pitch_align_forced = true;
-    }
     if (const char *s = getenv("SNPM_LONG_SCAN_ROWS")) ctx->long_scan_rows = atoll(s) < 0 ? INT64_MAX : atoll(s);
-    if (const char *s = getenv("SNPM_FULL_OCCUPANCY")) ctx->full_occupancy = atoi(s);
-    if (const char *s = getenv("SNPM_OCC_CAP")) ctx->occ_cap = atoi(s);
     if (const char *s = getenv("SNPM_F1_SLAB_BYTES")) ctx->f1_slab_bytes = std::max<int64_t>(1, atoll(s));
     if (const char *s = getenv("SNPM_ACC_MAJOR")) ctx->use_acc_major = atoi(s);
     if (const char *s = getenv("SNPM_ACC_MAJOR_MIN_ROWS")) ctx->acc_major_min_rows = atoll(s);
     if (const char *s = getenv("SNPM_DEBUG_REEVAL")) ctx->debug_reeval = atoi(s);
     if (const char *s = getenv("SNPM_PACKED_SPLIT")) ctx->packed_split = atoi(s) != 0;
-    if (const char *s = getenv("SNPM_STRICT4")) ctx->strict4 = atoi(s);
     if (const char *s = getenv("SNPM_ONCE_FUSED")) ctx->once_fused = atoi(s) != 0;
-    if (const char *s = getenv("SNPM_ONCE_ZEROCOPY")) ctx->once_zero_copy = atoi(s) != 0;
     if (const char *s = getenv("SNPM_DEBUG_MAX_PARTS")) ctx->debug_max_parts = atoi(s);
-    if (const char *s = getenv("SNPM_FUSED_REDUCE")) ctx->fused_reduce = atoi(s) != 0;
-    if (const char *s = getenv("SNPM_EVEN_TILES")) ctx->even_tiles = atoi(s) != 0;
     if (const char *s = getenv("SNPM_ONCE_TAIL")) ctx->once_tail = atoi(s) != 0;
     if (const char *s = getenv("SNPM_BATCH_SHARED")) ctx->batch_shared = atoi(s) < 0 ? -1 : (atoi(s) ? 1 : 0);
     if (const char *s = getenv("SNPM_SHARED_DIGITS")) ctx->shared_digits = atoi(s) <= 0 ? 0 : std::min(7, std::max(3, atoi(s)));
     if (const char *s = getenv("SNPM_SHARED_MIN_DENSITY")) ctx->shared_min_density = atof(s);
-    if (const char *s = getenv("SNPM_SHARED_FILL")) ctx->shared_fill = atoi(s) != 0;
     if (const char *s = getenv("SNPM_SHARED_WS_MB")) ctx->shared_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_SHARED_TILES")) ctx->shared_force_tiles = std::max(0, atoi(s));
-    if (const char *s = getenv("SNPM_SHARED_PROBE")) ctx->shared_probe = atoi(s) != 0;
-    if (const char *s = getenv("SNPM_SHARED_PARTS")) ctx->shared_parts = std::max(1, std::min(8, atoi(s)));
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -605,7 +546,7 @@ int snpm_destroy(snpm_ctx *ctx)
                        &ctx->ws_seg_desc, &ctx->ws_eseg, &ctx->ws_pairs, &ctx->ws_pair_sums, &ctx->ws_bscore, &ctx->ws_bninfo, &ctx->ws_bout,
                        &ctx->ws_blut, &ctx->ws_brows, &ctx->ws_brows32, &ctx->ws_bw, &ctx->ws_bcodes,
                        &ctx->ws_sh_bitmap, &ctx->ws_sh_wordbase, &ctx->ws_sh_blocks, &ctx->ws_sh_urows, &ctx->ws_sh_meta, &ctx->ws_sh_A,
-                       &ctx->ws_sh_pos, &ctx->ws_sh_partial, &ctx->ws_tickets};
+                       &ctx->ws_sh_pos, &ctx->ws_sh_partial};
         for (Buf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -623,9 +564,6 @@ int snpm_destroy(snpm_ctx *ctx)
         if (ctx->compute_mark) (void)hipEventDestroy(ctx->compute_mark);
         if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
         if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-        for (auto &ev : ctx->aux_ev)
-            if (ev) (void)hipEventDestroy(ev);
-        if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
     }
     ctx->qcache.clear();
     host_pool_destroy(ctx);

@@ -45,7 +45,7 @@ double efast_bound(const snpm_query *q, const FastGeom &g)
     // (int8 kernel: an accumulator takes one addition per row of its epoch = EPOCH_TILES tiles of g.tile_rows rows; the packed
     // kernels add pre-summed quads of rows or run on integer weights only: the static_asserts beside Q4_RUN keep them below
     // EPOCH_TILES * TILE_ROWS additions per epoch)
-    const int64_t epoch_adds = (int64_t)EPOCH_TILES * (g.bpl == 4 ? std::max(g.tile_rows, TILE_ROWS) : TILE_ROWS);
+    const int64_t epoch_adds = (int64_t)EPOCH_TILES * (g.packed ? TILE_ROWS : std::max(g.tile_rows, TILE_ROWS));
     const double m = (double)(std::min<int64_t>(g.part_rows, epoch_adds) + REDUCE_GROUP + g.n_groups + 2);
     return (q->wsum * (m * u / (1.0 - m * u))) * 1.0000001;
 }
@@ -65,7 +65,7 @@ int fast_tile_rows(const snpm_query *q, bool bits)
     // (panels of one or two waves keep the 128-row tiles: their blocks are small, the 16 KB of a long tile would bound the
     // resident blocks -- 256 accessions x 100M rows 0.528 -> 0.597 of HBM peak, 512 accessions 0.685 -> 0.773,
     // profiles/r03j_ab_int8_narrow.txt)
-    const bool long_tiles = q->n >= p->ctx->long_scan_rows && pick_bpl(p->ctx, p->n_acc) == 4 && p->n_acc > 2 * WAVE * 4;
+    const bool long_tiles = q->n >= p->ctx->long_scan_rows && p->n_acc > 2 * WAVE * 4;
     return long_tiles ? LONG_TILE_ROWS : TILE_ROWS;
 }
 
@@ -80,8 +80,7 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
     const bool gather = q->d_row_idx != nullptr;
     // packed panels: 16 accessions (one dword) per lane and row, four rows per table lookup (k_fast_packed_q4)
     const bool p16 = p->packed != 0;
-    const int bpl = p16 ? 16 : pick_bpl(ctx, p->n_acc);
-    const bool bits = p16 && q->hard01 && ctx->bits_path;      // counts instead of weighted sums
+    const bool bits = p16 && q->hard01;     // counts instead of weighted sums
     const int tile_rows = fast_tile_rows(q, bits);
     // k_fast_bits has no LDS tile and no barrier: one wave per block fills every wave slot of a CU evenly (measured on the
     // packed 10k x 50M panel: 22.4 ms with 1- or 2-wave blocks, 26.9 ms with the 5-wave blocks of the LUT kernels, 30.7 with 3)
@@ -90,15 +89,12 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
     // of exactly five waves (4097-5120 accessions): one 5-wave block instead of two 4-wave blocks with three idle waves
     // (17.5 against 23.4 ms on 5000 x 50M)
     const int wpb_fixed = bits ? 1 : (p16 ? q4_waves_per_block(p->n_acc) : 0);
-    FastGeom g0 = fast_geom(ctx, p->n_acc, q->n, 2, bpl, tile_rows, wpb_fixed);   // wpb does not depend on occupancy
+    FastGeom g0 = fast_geom(ctx, p->n_acc, q->n, 2, p16, tile_rows, wpb_fixed);   // wpb does not depend on occupancy
     int occ = 0;
-    const bool nt = ctx->nt_loads != 0;
     const int thr = WAVE * g0.wpb;
-    if (bits) (void)launch_bits(q, g0, skip, gather, nt, &occ, thr);
-    else if (p16) (void)launch_p16(q, g0, skip, gather, nt, &occ, thr);
-    else if (bpl == 16) occ = nt ? occ_b<16, true>(skip, gather, thr) : occ_b<16, false>(skip, gather, thr);
-    else if (bpl == 8) occ = nt ? occ_b<8, true>(skip, gather, thr) : occ_b<8, false>(skip, gather, thr);
-    else occ = nt ? occ_b<4, true>(skip, gather, thr) : occ_b<4, false>(skip, gather, thr);
+    if (bits) (void)launch_bits(q, g0, skip, gather, &occ, thr);
+    else if (p16) (void)launch_p16(q, g0, skip, gather, &occ, thr);
+    else occ = occ_b(skip, gather, thr);
     // Parts per resident block (round 3, profiles/r03j_ab_q4_parts_mult.txt, r03j_ab_parts_mult_all.txt): with as many parts as
     // resident blocks every block of k_fast_packed_q4 walks its tiles in step with all the others -- the whole chip builds tables,
     // then the whole chip looks up; eight times as many, shorter parts take the blocks out of step: 10 000 accessions 11.77 ->
@@ -111,18 +107,18 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
     // blocks per CU instead of the 5 / 4 / 4 the occupancy query allows -- a 1M-row sample takes 0.205 instead of 0.267 ms on 1135
     // accessions (5.66 vs 4.35 TB/s), 0.277 instead of 0.327 ms on 1500, 0.299 instead of 0.345 ms on 1700; 200k rows and blocks of
     // 1-4 or 8 waves do not care (profiles/r04_gather_occupancy.txt)
-    if (gather && !p16 && bpl == 4 && g0.wpb >= 5 && g0.wpb <= 7 && !ctx->full_occupancy) occ = std::min(occ, g0.wpb == 5 ? 4 : 3);
-    FastGeom g = fast_geom(ctx, p->n_acc, q->n, occ, bpl, tile_rows, wpb_fixed, kmult);
+    if (gather && !p16 && g0.wpb >= 5 && g0.wpb <= 7) occ = std::min(occ, g0.wpb == 5 ? 4 : 3);
+    FastGeom g = fast_geom(ctx, p->n_acc, q->n, occ, p16, tile_rows, wpb_fixed, kmult);
     // Short int8 queries (a sample's 200k gathered rows: one or two 128-row tiles per resident block): tiles of such a length that
     // every part walks the same number of them -- 1563 tiles over 1024 parts make the launch as long as its two-tile parts (76 %
     // of the blocks' time is work); with k = ceil(tiles / parts) tiles of ceil(n / (k parts)) rows (a multiple of 8) it is 94 %.
-    if (!p16 && bpl == 4 && tile_rows == TILE_ROWS && ctx->even_tiles && g.n_epochs == 1 && g.n_parts > 1) {
+    if (!p16 && tile_rows == TILE_ROWS && g.n_epochs == 1 && g.n_parts > 1) {
         const int64_t n_tiles = (q->n + TILE_ROWS - 1) / TILE_ROWS;
         const int64_t k = (n_tiles + g.n_parts - 1) / g.n_parts;
         if (k <= 8 && n_tiles > g.n_parts) {
             int64_t tr = ((q->n + k * g.n_parts - 1) / (k * g.n_parts) + 7) / 8 * 8;
             tr = std::max<int64_t>(32, std::min<int64_t>(TILE_ROWS, tr));
-            if (tr < TILE_ROWS) g = fast_geom(ctx, p->n_acc, q->n, occ, bpl, (int)tr, wpb_fixed, kmult);
+            if (tr < TILE_ROWS) g = fast_geom(ctx, p->n_acc, q->n, occ, p16, (int)tr, wpb_fixed, kmult);
         }
     }
     if (geom_out) *geom_out = g;
@@ -150,11 +146,9 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
             HIPCHK(ctx, hipMemsetAsync((double *)ctx->ws_part_score.p + off, 0, (size_t)g.n_parts * p->ld * sizeof(double), ctx->stream));
             HIPCHK(ctx, hipMemsetAsync((uint32_t *)ctx->ws_part_miss.p + off, 0, (size_t)g.n_parts * p->ld * sizeof(uint32_t), ctx->stream));
         }
-        if (bits) rc = launch_bits(q, g, skip, gather, nt, nullptr, thr);
-        else if (p16) rc = launch_p16(q, g, skip, gather, nt, nullptr, thr);
-        else if (bpl == 16) rc = nt ? launch_fast_b<16, true>(q, g, skip, gather) : launch_fast_b<16, false>(q, g, skip, gather);
-        else if (bpl == 8) rc = nt ? launch_fast_b<8, true>(q, g, skip, gather) : launch_fast_b<8, false>(q, g, skip, gather);
-        else rc = nt ? launch_fast_b<4, true>(q, g, skip, gather) : launch_fast_b<4, false>(q, g, skip, gather);
+        if (bits) rc = launch_bits(q, g, skip, gather, nullptr, thr);
+        else if (p16) rc = launch_p16(q, g, skip, gather, nullptr, thr);
+        else rc = launch_fast_b(q, g, skip, gather);
         if (rc) return rc;
     }
     {
@@ -164,30 +158,16 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
         const int64_t n_groups = q->n > 0 ? g.n_groups : 0;
         const double *eref = (certify && cert.flag) ? (const double *)q->cert_eref() : (const double *)nullptr;
         const double efast = certify ? efast_bound(q, g) : 0.0;
-        if (n_groups > 0 && n_groups <= 65535 && ctx->fused_reduce) {
-            // both steps in one launch (tickets per column block, zero between launches)
-            if (ctx->ws_tickets.cap < (size_t)cb * sizeof(unsigned)) {
-                rc = ensure(ctx, ctx->ws_tickets, std::max<size_t>((size_t)cb * sizeof(unsigned), 4096));
-                if (rc) return rc;
-                HIPCHK(ctx, hipMemsetAsync(ctx->ws_tickets.p, 0, ctx->ws_tickets.cap, ctx->stream));
-            }
-            hipLaunchKernelGGL(k_reduce_all, dim3(cb, (unsigned)n_groups), dim3(thr), 0, ctx->stream,
-                               (const double *)ctx->ws_part_score.p, (const uint32_t *)ctx->ws_part_miss.p, g.n_slots, p->ld, p->n_acc,
-                               q->n, (double *)ctx->ws_grp_score.p, (uint32_t *)ctx->ws_grp_miss.p, q->d_score, q->d_ninfo, eref, efast,
-                               ctx->debug_reeval, q->cert_cols(), q->cert_count(), REEVAL_CAP, (unsigned *)ctx->ws_tickets.p);
-            HIPCHK(ctx, hipGetLastError());
-        } else {
-            if (n_groups > 0) {
-                hipLaunchKernelGGL(k_reduce_groups, dim3(cb, (unsigned)n_groups), dim3(thr), 0, ctx->stream,
-                                   (const double *)ctx->ws_part_score.p, (const uint32_t *)ctx->ws_part_miss.p, g.n_slots,
-                                   p->ld, p->n_acc, (double *)ctx->ws_grp_score.p, (uint32_t *)ctx->ws_grp_miss.p);
-                HIPCHK(ctx, hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_reduce, dim3(cb), dim3(thr), 0, ctx->stream, (const double *)ctx->ws_grp_score.p,
-                               (const uint32_t *)ctx->ws_grp_miss.p, n_groups, p->ld, p->n_acc, q->n, q->d_score,
-                               q->d_ninfo, eref, efast, ctx->debug_reeval, q->cert_cols(), q->cert_count(), REEVAL_CAP);
+        if (n_groups > 0) {
+            hipLaunchKernelGGL(k_reduce_groups, dim3(cb, (unsigned)n_groups), dim3(thr), 0, ctx->stream,
+                               (const double *)ctx->ws_part_score.p, (const uint32_t *)ctx->ws_part_miss.p, g.n_slots,
+                               p->ld, p->n_acc, (double *)ctx->ws_grp_score.p, (uint32_t *)ctx->ws_grp_miss.p);
             HIPCHK(ctx, hipGetLastError());
         }
+        hipLaunchKernelGGL(k_reduce, dim3(cb), dim3(thr), 0, ctx->stream, (const double *)ctx->ws_grp_score.p,
+                           (const uint32_t *)ctx->ws_grp_miss.p, n_groups, p->ld, p->n_acc, q->n, q->d_score,
+                           q->d_ninfo, eref, efast, ctx->debug_reeval, q->cert_cols(), q->cert_count(), REEVAL_CAP);
+        HIPCHK(ctx, hipGetLastError());
     }
     return SNPM_OK;
 }

@@ -2,42 +2,33 @@
 // Part of the one translation unit of libsnpmatch_hip.so: included by snpm_api.hip at this place, not on its own.
 // ---- launch geometry of the fast pass ---------------------------------------------------------
 struct FastGeom {
-    int bpl, wpb;
+    bool packed;            // a lane covers 16 accessions (one dword of a packed row) instead of 4 (one dword of an int8 row)
+    int wpb;
     int tile_rows = TILE_ROWS;
     int64_t n_wc, n_colblocks, n_parts, part_rows;
     int64_t n_epochs, n_slots, n_groups;      // partial slots = n_epochs * n_parts, reduced in groups
 };
 
-template <int BPL, bool SKIP, bool GATHER, bool NT>
+template <bool SKIP, bool GATHER>
 int occupancy_of(int threads)
 {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast<BPL, SKIP, GATHER, NT>, threads, 0) != hipSuccess) nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast<SKIP, GATHER>, threads, 0) != hipSuccess) nb = 0;
     return nb;
 }
 
-int pick_bpl(snpm_ctx *ctx, int64_t n_acc)
-{
-    // Bytes per lane of the fast pass.  Measured on MI355X (10k x 6.25M panel, round 1): 4 B per lane
-    // streams at 6.5 TB/s, 8 B at 4.4, 16 B at 5.3 -- the kernel is latency-bound and the narrow layout
-    // keeps the most waves resident; it also has the best lane utilisation for every n_acc.  The wider
-    // instantiations stay selectable (SNPM_FORCE_BPL) for experiments.
-    (void)n_acc;
-    if (ctx->force_bpl == 8 || ctx->force_bpl == 16) return ctx->force_bpl;
-    return 4;
-}
-
-FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint, int bpl, int tile_rows = TILE_ROWS,
+// The int8 fast pass reads 4 bytes per lane and row.  Measured on MI355X (10k x 6.25M panel, round 1): 4 B per lane
+// streams at 6.5 TB/s, 8 B at 4.4, 16 B at 5.3 -- the kernel is latency-bound and the narrow layout
+// keeps the most waves resident; it also has the best lane utilisation for every n_acc.
+FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint, bool packed, int tile_rows = TILE_ROWS,
                    int wpb_fixed = 0, int kernel_parts_mult = 1)
 {
     FastGeom g;
-    g.bpl = bpl;
+    g.packed = packed;
     g.tile_rows = tile_rows;
-    const int64_t span = (int64_t)WAVE * bpl;
+    const int64_t span = (int64_t)WAVE * (packed ? 16 : 4);
     g.n_wc = std::max<int64_t>(1, (n_acc + span - 1) / span);
-    if (ctx->force_wpb >= 1 && ctx->force_wpb <= MAX_WAVES_PER_BLOCK) {
-        g.wpb = (int)std::min<int64_t>(ctx->force_wpb, g.n_wc);
-    } else if (wpb_fixed > 0) {
+    if (wpb_fixed > 0) {
         g.wpb = (int)std::min<int64_t>(wpb_fixed, g.n_wc);
     } else if (g.n_wc <= 8) {
         g.wpb = (int)g.n_wc;
@@ -64,7 +55,7 @@ FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint,
     // 5000 x 12.5M), while 6- to 8-wave blocks and short scans (1135 x 11M, 14 GB) are 1-3 % better at full
     // occupancy.  The part count stays a multiple of the CU count either way (uneven counts cost 5-10 %).
     const int64_t pitch_bytes = ((n_acc + 255) / 256) * 256;
-    if (bpl == 4 && occ_blocks_hint > 0 && !ctx->full_occupancy && (g.wpb == 4 || g.wpb == 5) &&
+    if (!packed && occ_blocks_hint > 0 && (g.wpb == 4 || g.wpb == 5) &&
         n * pitch_bytes >= (int64_t(32) << 30))
         occ = std::min(occ, std::max(3, 18 / g.wpb));
     // Full 8-wave blocks (n_acc within 8 waves of a multiple of 2048): TWO resident blocks per CU instead of the three that fit
@@ -72,24 +63,24 @@ FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint,
     // (round 3, profiles/r03b_ab_occ_cap*.txt: 10 000 x 20M 0.791 -> 0.808 of HBM peak, 8192 x 24M 0.767 -> 0.787, 16 384 x 12M
     // 0.758 -> 0.779, 6144 x 30M 0.822 -> 0.833, 20 480 x 9M 0.805 -> 0.821, 4096 x 40M 0.796 -> 0.804, 2048 x 50M equal), while
     // 5- and 7-wave blocks lose 10-25 % with it (1252 / 2500 / 5000 / 12 500 accessions) and keep their own cap above.
-    if (bpl == 4 && occ_blocks_hint > 0 && !ctx->full_occupancy && g.wpb == 8 &&
+    if (!packed && occ_blocks_hint > 0 && g.wpb == 8 &&
         n * pitch_bytes >= (int64_t(4) << 30))
         occ = std::min(occ, 2);
-    if (ctx->occ_cap > 0) occ = std::min(occ, ctx->occ_cap);
     // one-wave blocks of the int8 kernel (panels of up to 256 accessions): four times as many parts as resident blocks
     // (256 x 100M rows 0.597 -> 0.754 of HBM peak with the 128-row tiles; two-wave blocks and wider: no gain)
-    const int narrow_mult = (bpl == 4 && g.wpb == 1 && occ_blocks_hint > 0 && ctx->parts_mult == 1) ? 4 : 1;
+    const int narrow_mult = (!packed && g.wpb == 1 && occ_blocks_hint > 0) ? 4 : 1;
     const int64_t n_tiles = std::max<int64_t>(1, (n + tile_rows - 1) / tile_rows);
     // kernel_parts_mult: k_fast_packed_q4 runs best with MORE parts than resident blocks (run_fast) -- as long as a part keeps
     // eight tiles or so: every part costs a slot of partial sums to write and to add up, which on short scans outweighs the
     // gain (1135 accessions x 11M rows with 16 parts per block: kernel 1.07 -> 1.09 ms, the step 1.11 -> 1.25 ms; 32 / 16 / 8 / 4
     // tiles per part by the time of the whole step: profiles/r03j_ab_part_min_tiles.txt)
+    constexpr int64_t kPartMinTiles = 8;
     int kmult = 1;
-    if (ctx->parts_mult == 1 && kernel_parts_mult > 1 && g.wpb != 5) {       // (the one 5-wave block shape, 4097-5120 accessions: 2 / 4 parts per block lose 10 / 2 %, 8 gain 1 %)
+    if (kernel_parts_mult > 1 && g.wpb != 5) {       // (the one 5-wave block shape, 4097-5120 accessions: 2 / 4 parts per block lose 10 / 2 %, 8 gain 1 %)
         const int64_t base_parts = std::max<int64_t>(1, (int64_t)ctx->n_cu * occ * narrow_mult / g.n_colblocks);
-        kmult = (int)std::max<int64_t>(1, std::min<int64_t>(kernel_parts_mult, n_tiles / (base_parts * std::max(1, ctx->part_min_tiles))));
+        kmult = (int)std::max<int64_t>(1, std::min<int64_t>(kernel_parts_mult, n_tiles / (base_parts * kPartMinTiles)));
     }
-    int64_t resident = (int64_t)ctx->n_cu * occ * std::max(1, ctx->parts_mult) * narrow_mult * kmult;
+    int64_t resident = (int64_t)ctx->n_cu * occ * narrow_mult * kmult;
     int64_t n_parts = std::max<int64_t>(1, resident / g.n_colblocks);
     n_parts = std::min(n_parts, n_tiles);                    // part p scores tiles p, p+P, p+2P, ...
     if (ctx->debug_max_parts > 0) n_parts = std::min<int64_t>(n_parts, ctx->debug_max_parts);   // tests: long parts
@@ -103,7 +94,7 @@ FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint,
     return g;
 }
 
-template <int BPL, bool SKIP, bool GATHER, bool NT>
+template <bool SKIP, bool GATHER>
 int launch_fast_t(snpm_query *q, const FastGeom &g)
 {
     snpm_ctx *ctx = q->panel->ctx;
@@ -111,24 +102,23 @@ int launch_fast_t(snpm_query *q, const FastGeom &g)
     dim3 grid((unsigned)g.n_colblocks, (unsigned)g.n_parts);
     dim3 block(WAVE * g.wpb);
     ProfScope ps(ctx, PK_FAST);
-    if (BPL == 4 && g.tile_rows == LONG_TILE_ROWS)          // long scans: tiles of LONG_TILE_ROWS rows (fast_tile_rows)
-        hipLaunchKernelGGL((k_fast<BPL, SKIP, GATHER, NT, false, (BPL == 4 ? LONG_TILE_ROWS : TILE_ROWS)>), grid, block, 0, ctx->stream, p->d,
+    if (g.tile_rows == LONG_TILE_ROWS)          // long scans: tiles of LONG_TILE_ROWS rows (fast_tile_rows)
+        hipLaunchKernelGGL((k_fast<SKIP, GATHER, false, LONG_TILE_ROWS>), grid, block, 0, ctx->stream, p->d,
                            p->pitch, q->d_row_idx, q->row0, q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p,
                            p->ld, (const int64_t *)nullptr);
     else
-        hipLaunchKernelGGL((k_fast<BPL, SKIP, GATHER, NT>), grid, block, 0, ctx->stream, p->d, p->pitch, q->d_row_idx, q->row0,
+        hipLaunchKernelGGL((k_fast<SKIP, GATHER>), grid, block, 0, ctx->stream, p->d, p->pitch, q->d_row_idx, q->row0,
                            q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld,
-                           (const int64_t *)nullptr, (BPL == 4 && g.tile_rows < TILE_ROWS) ? g.tile_rows : 0);
+                           (const int64_t *)nullptr, g.tile_rows < TILE_ROWS ? g.tile_rows : 0);
     HIPCHK(ctx, hipGetLastError());
     return SNPM_OK;
 }
 
-template <int BPL, bool NT>
 int launch_fast_b(snpm_query *q, const FastGeom &g, bool skip, bool gather)
 {
     if (skip)
-        return gather ? launch_fast_t<BPL, true, true, NT>(q, g) : launch_fast_t<BPL, true, false, NT>(q, g);
-    return gather ? launch_fast_t<BPL, false, true, NT>(q, g) : launch_fast_t<BPL, false, false, NT>(q, g);
+        return gather ? launch_fast_t<true, true>(q, g) : launch_fast_t<true, false>(q, g);
+    return gather ? launch_fast_t<false, true>(q, g) : launch_fast_t<false, false>(q, g);
 }
 
 // block shape of k_fast_packed_q4 (a wave covers 1024 accessions): see run_fast
@@ -155,84 +145,80 @@ static int q4_waves_per_block(int64_t n_acc)
 }
 
 // rows per LDS tile of k_fast_packed_q4 by block size (see the kernel): blocks of fewer than four waves take smaller tiles so that
-// LDS does not bound the resident waves of a CU (SNPM_Q4_TILE_ROWS = 16 / 32 / 64 forces one size)
-static int q4_tile_rows(const snpm_ctx *ctx, int wpb)
+// LDS does not bound the resident waves of a CU
+static int q4_tile_rows(int wpb)
 {
-    if (ctx->q4_tile_rows == 16 || ctx->q4_tile_rows == 32 || ctx->q4_tile_rows == 64) return ctx->q4_tile_rows;
     return wpb >= 4 ? 64 : (wpb >= 2 ? 32 : 16);
 }
 
-template <bool SKIP, bool GATHER, bool NT, int TR>
+template <bool SKIP, bool GATHER, int TR>
 int launch_p16_t(snpm_query *q, const FastGeom &g, int *occ_out, int threads)
 {
     snpm_ctx *ctx = q->panel->ctx;
     snpm_panel *p = q->panel;
     if (occ_out) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast_packed_q4<SKIP, GATHER, NT, false, TR>, threads, 0) != hipSuccess) nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast_packed_q4<SKIP, GATHER, false, TR>, threads, 0) != hipSuccess) nb = 0;
         *occ_out = nb;
         return SNPM_OK;
     }
     dim3 grid((unsigned)g.n_colblocks, (unsigned)g.n_parts);
     dim3 block(WAVE * g.wpb);
     ProfScope ps(ctx, PK_FAST);
-    hipLaunchKernelGGL((k_fast_packed_q4<SKIP, GATHER, NT, false, TR>), grid, block, 0, ctx->stream, p->d, p->kpitch, q->d_row_idx,
+    hipLaunchKernelGGL((k_fast_packed_q4<SKIP, GATHER, false, TR>), grid, block, 0, ctx->stream, p->d, p->kpitch, q->d_row_idx,
                        q->row0, q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, p->n_acc,
                        p->desc);
     HIPCHK(ctx, hipGetLastError());
     return SNPM_OK;
 }
 
-int launch_p16(snpm_query *q, const FastGeom &g, bool skip, bool gather, bool nt, int *occ_out, int threads)
+int launch_p16(snpm_query *q, const FastGeom &g, bool skip, bool gather, int *occ_out, int threads)
 {
-    const int tr = q4_tile_rows(q->panel->ctx, threads / WAVE);
-#define P16_CASE(S, G, N)                                                                           \
-    if (skip == S && gather == G && nt == N) {                                                      \
-        if (tr == 16) return launch_p16_t<S, G, N, 16>(q, g, occ_out, threads);                     \
-        if (tr == 32) return launch_p16_t<S, G, N, 32>(q, g, occ_out, threads);                     \
-        return launch_p16_t<S, G, N, 64>(q, g, occ_out, threads);                                   \
+    const int tr = q4_tile_rows(threads / WAVE);
+#define P16_CASE(S, G)                                                                              \
+    if (skip == S && gather == G) {                                                                 \
+        if (tr == 16) return launch_p16_t<S, G, 16>(q, g, occ_out, threads);                        \
+        if (tr == 32) return launch_p16_t<S, G, 32>(q, g, occ_out, threads);                        \
+        return launch_p16_t<S, G, 64>(q, g, occ_out, threads);                                      \
     }
-    P16_CASE(false, false, false) P16_CASE(false, false, true) P16_CASE(false, true, false) P16_CASE(false, true, true)
-    P16_CASE(true, false, false)  P16_CASE(true, false, true)  P16_CASE(true, true, false)  P16_CASE(true, true, true)
+    P16_CASE(false, false) P16_CASE(false, true) P16_CASE(true, false) P16_CASE(true, true)
 #undef P16_CASE
     return SNPM_ERR_STATE;
 }
 
 // hard-call samples on packed panels (k_fast_bits)
-template <bool SKIP, bool GATHER, bool NT>
+template <bool SKIP, bool GATHER>
 int launch_bits_t(snpm_query *q, const FastGeom &g, int *occ_out, int threads)
 {
     snpm_ctx *ctx = q->panel->ctx;
     snpm_panel *p = q->panel;
     if (occ_out) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast_bits<SKIP, GATHER, NT>, threads, 0) != hipSuccess) nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast_bits<SKIP, GATHER>, threads, 0) != hipSuccess) nb = 0;
         *occ_out = nb;
         return SNPM_OK;
     }
     ProfScope ps(ctx, PK_FAST);
     // grid = (parts, column blocks): the part is the fast block index (XCD balance, see the kernel)
-    hipLaunchKernelGGL((k_fast_bits<SKIP, GATHER, NT>), dim3((unsigned)g.n_parts, (unsigned)g.n_colblocks), dim3(WAVE * g.wpb), 0,
+    hipLaunchKernelGGL((k_fast_bits<SKIP, GATHER>), dim3((unsigned)g.n_parts, (unsigned)g.n_colblocks), dim3(WAVE * g.wpb), 0,
                        ctx->stream, p->d, p->kpitch, q->d_row_idx, q->row0, q->n, (const uint8_t *)q->d_wbits,
                        (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, p->n_acc, p->desc);
     HIPCHK(ctx, hipGetLastError());
     return SNPM_OK;
 }
 
-int launch_bits(snpm_query *q, const FastGeom &g, bool skip, bool gather, bool nt, int *occ_out, int threads)
+int launch_bits(snpm_query *q, const FastGeom &g, bool skip, bool gather, int *occ_out, int threads)
 {
-#define BITS_CASE(S, G, N) if (skip == S && gather == G && nt == N) return launch_bits_t<S, G, N>(q, g, occ_out, threads)
-    BITS_CASE(false, false, false); BITS_CASE(false, false, true); BITS_CASE(false, true, false); BITS_CASE(false, true, true);
-    BITS_CASE(true, false, false);  BITS_CASE(true, false, true);  BITS_CASE(true, true, false);  BITS_CASE(true, true, true);
+#define BITS_CASE(S, G) if (skip == S && gather == G) return launch_bits_t<S, G>(q, g, occ_out, threads)
+    BITS_CASE(false, false); BITS_CASE(false, true); BITS_CASE(true, false); BITS_CASE(true, true);
 #undef BITS_CASE
     return SNPM_ERR_STATE;
 }
 
-template <int BPL, bool NT>
 int occ_b(bool skip, bool gather, int threads)
 {
-    if (skip) return gather ? occupancy_of<BPL, true, true, NT>(threads) : occupancy_of<BPL, true, false, NT>(threads);
-    return gather ? occupancy_of<BPL, false, true, NT>(threads) : occupancy_of<BPL, false, false, NT>(threads);
+    if (skip) return gather ? occupancy_of<true, true>(threads) : occupancy_of<true, false>(threads);
+    return gather ? occupancy_of<false, true>(threads) : occupancy_of<false, false>(threads);
 }
 
 int ensure_lut(snpm_query *q, int skip)

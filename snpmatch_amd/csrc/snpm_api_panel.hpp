@@ -9,7 +9,7 @@
 static void packed_split_of(const snpm_ctx *ctx, int64_t n_acc, int64_t *main_pitch, int64_t *tail_pitch)
 {
     *main_pitch = *tail_pitch = 0;
-    if (!ctx->packed_split || ctx->pitch_align_forced) return;
+    if (!ctx->packed_split) return;
     if (const char *e = getenv("SNPM_PACKED_SPLIT"))               // also read per panel: one process may hold both layouts (tests)
         if (atoi(e) == 0) return;
     const int64_t row_bytes = (n_acc + 3) / 4;
@@ -29,8 +29,8 @@ static int64_t panel_row_pitch(const snpm_ctx *ctx, int64_t n_acc, int packed)
         packed_split_of(ctx, n_acc, &mp, &tp);
         if (tp) return mp + tp;
     }
-    int64_t align = ctx->pitch_align;
-    if (!packed && !ctx->pitch_align_forced) {
+    int64_t align = 256;
+    if (!packed) {
         const int64_t p256 = (n_acc + 255) / 256 * 256, p128 = (n_acc + 127) / 128 * 128;
         if ((p256 - p128) * 20 >= p256) align = 128;
     }
@@ -39,7 +39,7 @@ static int64_t panel_row_pitch(const snpm_ctx *ctx, int64_t n_acc, int packed)
     // per row (round 3, profiles/r03k_ab_pow2_pitch.txt: 8192 accessions int8 0.801 -> 0.827 of HBM peak, 16 384: 0.780 -> 0.797,
     // 32 768 accessions packed with hard calls 0.697 -> 0.741, with PL weights +1 %; at 4 KiB the gain is 1 %, at 2 KiB the
     // padding costs more than it brings)
-    if (!ctx->pitch_align_forced && pitch % 8192 == 0) pitch += 256;
+    if (pitch % 8192 == 0) pitch += 256;
     return pitch;
 }
 

@@ -25,15 +25,14 @@ constexpr int SEG_PAIR_CAP = 32768;
 int *seg_pair_count(snpm_ctx *ctx) { return (int *)ctx->ws_pairs.p; }
 int32_t *seg_pairs(snpm_ctx *ctx) { return (int32_t *)((char *)ctx->ws_pairs.p + 16); }
 
-template <bool NT>
 static int launch_q4_seg(snpm_ctx *ctx, const SegJob &j, dim3 grid, dim3 block, int64_t n_parts, const int64_t *d_desc)
 {
     snpm_panel *p = j.p;
     const bool gather = j.d_row_idx != nullptr;
     ProfScope ps(ctx, PK_FAST);
-    const int tr = q4_tile_rows(ctx, (int)(block.x / WAVE));
+    const int tr = q4_tile_rows((int)(block.x / WAVE));
 #define LAUNCH_SEG_TR(S, G, TR)                                                                                   \
-    hipLaunchKernelGGL((k_fast_packed_q4<S, G, NT, true, TR>), grid, block, 0, ctx->stream, p->d, p->kpitch, j.d_row_idx, j.row0, \
+    hipLaunchKernelGGL((k_fast_packed_q4<S, G, true, TR>), grid, block, 0, ctx->stream, p->d, p->kpitch, j.d_row_idx, j.row0, \
                        n_parts, j.d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, p->n_acc, p->desc, d_desc)
 #define LAUNCH_SEG(S, G)                                                                                          \
     do {                                                                                                          \
@@ -52,14 +51,13 @@ static int launch_q4_seg(snpm_ctx *ctx, const SegJob &j, dim3 grid, dim3 block, 
     return SNPM_OK;
 }
 
-template <int BPL, bool NT>
 static int launch_fast_seg(snpm_ctx *ctx, const SegJob &j, dim3 grid, dim3 block, int64_t n_parts, const int64_t *d_desc)
 {
     snpm_panel *p = j.p;
     const bool gather = j.d_row_idx != nullptr;
     ProfScope ps(ctx, PK_FAST);
 #define LAUNCH_SEG(S, G)                                                                                          \
-    hipLaunchKernelGGL((k_fast<BPL, S, G, NT, true>), grid, block, 0, ctx->stream, p->d, p->pitch, j.d_row_idx, j.row0,    \
+    hipLaunchKernelGGL((k_fast<S, G, true>), grid, block, 0, ctx->stream, p->d, p->pitch, j.d_row_idx, j.row0,    \
                        n_parts, j.d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, d_desc)
     if (j.skip) {
         if (gather) LAUNCH_SEG(true, true); else LAUNCH_SEG(true, false);
@@ -86,10 +84,10 @@ static int seg_plan(snpm_ctx *ctx, SegJob &j, SegPlan &pl)
 {
     snpm_panel *p = j.p;
     const int64_t n_seg = j.n_seg;
-    // int8: a dword (4 accessions) per lane, k_fast<4, SEG>; packed: a dword (16 accessions) per lane, k_fast_packed_q4<SEG>
+    // int8: a dword (4 accessions) per lane, k_fast<SEG>; packed: a dword (16 accessions) per lane, k_fast_packed_q4<SEG>
     const bool q4 = p->packed != 0;
-    pl.g0 = q4 ? fast_geom(ctx, p->n_acc, TILE_ROWS, 2, 16, TILE_ROWS, q4_waves_per_block(p->n_acc))
-               : fast_geom(ctx, p->n_acc, TILE_ROWS, 2, 4, TILE_ROWS);
+    pl.g0 = q4 ? fast_geom(ctx, p->n_acc, TILE_ROWS, 2, true, TILE_ROWS, q4_waves_per_block(p->n_acc))
+               : fast_geom(ctx, p->n_acc, TILE_ROWS, 2, false, TILE_ROWS);
     int64_t total_tiles = 0, kmax = 1;
     for (int64_t s = 0; s < n_seg; ++s) {
         const int64_t len = j.seg_off[s + 1] - j.seg_off[s];
@@ -99,7 +97,7 @@ static int seg_plan(snpm_ctx *ctx, SegJob &j, SegPlan &pl)
     // enough parts to fill the chip a few times over
     // (int8 panels: 32 parts per CU and column block, gathered batches of 64 samples 3.07 -> 2.72 ms with them; packed panels
     // measure the same from 8 to 64 and keep 8 -- profiles/r03j_ab_seg_blocks.txt)
-    const int per_cu = ctx->seg_blocks_per_cu > 0 ? ctx->seg_blocks_per_cu : (q4 ? 8 : 32);
+    const int per_cu = q4 ? 8 : 32;
     // ... but k_reduce_seg adds a segment's slots one after the other: a batch of 8 samples cut into 8192 parts spent 0.21 of its
     // 0.76 ms there (1024 dependent additions per accession); at most 256 slots per segment
     const int64_t want_blocks = std::max<int64_t>(1, std::min<int64_t>((int64_t)ctx->n_cu * per_cu / std::max<int64_t>(1, pl.g0.n_colblocks),
@@ -184,10 +182,8 @@ static int seg_launch(snpm_ctx *ctx, const SegJob &j, const SegPlan &pl, int64_t
         const unsigned gy = (unsigned)std::min<int64_t>(np, 65535);
         const unsigned gz = (unsigned)((np + gy - 1) / gy);
         dim3 grid((unsigned)pl.g0.n_colblocks, gy, gz), block(WAVE * pl.g0.wpb);
-        const bool nt = ctx->nt_loads != 0;
         const int64_t *desc = pl.d_desc + 3 * p0;
-        if (p->packed) rc = nt ? launch_q4_seg<true>(ctx, j, grid, block, np, desc) : launch_q4_seg<false>(ctx, j, grid, block, np, desc);
-        else rc = nt ? launch_fast_seg<4, true>(ctx, j, grid, block, np, desc) : launch_fast_seg<4, false>(ctx, j, grid, block, np, desc);
+        rc = p->packed ? launch_q4_seg(ctx, j, grid, block, np, desc) : launch_fast_seg(ctx, j, grid, block, np, desc);
         if (rc) return rc;
     }
     ProfScope ps(ctx, PK_REDUCE);

@@ -61,7 +61,7 @@ static int shared_rows_try(snpm_ctx *ctx, SegJob &j, bool forced, SharedStats &s
     long long *h_meta = (long long *)ctx->h_pinned;
     const int64_t *h_seg_off = (const int64_t *)((char *)ctx->h_pinned + 64);
     memcpy((char *)ctx->h_pinned + 64, j.seg_off, ((size_t)n_seg + 1) * 8);
-    if (!forced && p->n_snp >= 4096 && ctx->shared_probe) {
+    if (!forced && p->n_snp >= 4096) {
         // automatic policy: look at 1/32 of the panel first (the batch's calls below row n_snp / 32); scattered marker sets are
         // declined here, before the full pass over every row and weight of the batch
         const int64_t row_limit = (p->n_snp / 32 + 31) / 32 * 32;
@@ -147,8 +147,7 @@ static int shared_rows_try(snpm_ctx *ctx, SegJob &j, bool forced, SharedStats &s
             // (a filler tile then lies on two or three XCDs: 64 samples 27 x 32 -> 27 x 36 wave tiles on 1024 slots)
             const int64_t rounds = ((int64_t)best_m * blocks_per_tile + cu_per_xcd - 1) / cu_per_xcd;
             const int64_t idle = rounds * cu_per_xcd - (int64_t)best_m * blocks_per_tile;
-            const bool one_launch = !(ctx->shared_parts > 1 && ctx->aux_stream);
-            if (one_launch && ctx->shared_fill) T += 8 * idle / blocks_per_tile;
+            T += 8 * idle / blocks_per_tile;
         }
         if (T * 16 > n_steps) T = std::max<int64_t>(1, n_steps / 16);
         steps_per_tile = ((n_steps + T - 1) / T + SH_DEPTH - 1) / SH_DEPTH * SH_DEPTH;
@@ -190,54 +189,39 @@ static int shared_rows_try(snpm_ctx *ctx, SegJob &j, bool forced, SharedStats &s
         // (32 .. 512 blocks per sample: the same 38 us, it moves 250 MB)
         hipLaunchKernelGGL(k_sh_pos, dim3(gx, (unsigned)s_pass), dim3(256), 0, ctx->stream, j.d_row_idx, (const int64_t *)d_seg_off, s_base,
                            (const uint32_t *)d_bitmap, (const uint32_t *)d_wordbase, (uint32_t *)ctx->ws_sh_pos.p, ld_pos);
-        // The pass in parts of whole row tiles (SNPM_SHARED_PARTS > 1, an experiment that measured SLOWER and is off by default): the
-        // digits of part i + 1 are laid out (k_sh_expand, on the auxiliary stream: memory latency) while part i is contracted
-        // (k_sh_mfma, one wave per SIMD: the matrix cores).  One part = everything on the main stream.
-        const int m_tiles = (tiles + 7) / 8;                                // tiles come in sets of 8 (one per XCD)
-        const int n_parts = (ctx->shared_parts > 0 && ctx->aux_stream) ? std::max(1, std::min(ctx->shared_parts, m_tiles)) : 1;
-        const bool overlap = n_parts > 1;
-        if (overlap) {
-            HIPCHK(ctx, hipEventRecord(ctx->aux_ev[0], ctx->stream));       // k_sh_pos (and the previous pass's readers of A) before the first expansion
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
-        }
-        for (int part = 0; part < n_parts; ++part) {
-            const int t0 = 8 * (int)((int64_t)m_tiles * part / n_parts), t1 = std::min(tiles, 8 * (int)((int64_t)m_tiles * (part + 1) / n_parts));
-            if (t1 <= t0) continue;
-            const int64_t k0 = (int64_t)t0 * spt, k1 = std::min<int64_t>(n_steps, (int64_t)t1 * spt);
-            hipStream_t es = overlap ? ctx->aux_stream : ctx->stream;
-            {
-                ProfScope ps(ctx, PK_LUT);
-                const dim3 eg((unsigned)s_pass, (unsigned)std::min<int64_t>(65535, (k1 - k0 + 127) / 128));
+        // One expansion (k_sh_expand: memory latency) and one contraction (k_sh_mfma, one wave per SIMD: the matrix cores) per pass,
+        // on one stream.  Laying out the digits of a part of the tiles on a second stream beside the previous part's contraction
+        // measured slower and was removed (64 x 200k x 1135: 1.08 ms against 1.28 / 1.33 / 1.91 ms in 2 / 4 / 8 parts: the layout's
+        // waves take issue slots and L1 from the contraction, and a part no longer fills the chip;
+        // profiles/r05_shared_two_stream_parts_dead_end.txt)
+        {
+            ProfScope ps(ctx, PK_LUT);
+            const dim3 eg((unsigned)s_pass, (unsigned)std::min<int64_t>(65535, (n_steps + 127) / 128));
 #define LAUNCH_EXPAND(D)                                                                                                     \
-    hipLaunchKernelGGL((k_sh_expand<D>), eg, dim3(256), 0, es, (const uint32_t *)ctx->ws_sh_pos.p, ld_pos, j.d_w, s_pass, j.skip,  \
-                       k0, k1 - k0, steps_ld, (sh_v4i *)ctx->ws_sh_A.p, d_nonint + s_base, d_meta)
-                switch (digits) {
-                case 3: LAUNCH_EXPAND(3); break;
-                case 4: LAUNCH_EXPAND(4); break;
-                case 5: LAUNCH_EXPAND(5); break;
-                case 6: LAUNCH_EXPAND(6); break;
-                default: LAUNCH_EXPAND(7); break;
-                }
+    hipLaunchKernelGGL((k_sh_expand<D>), eg, dim3(256), 0, ctx->stream, (const uint32_t *)ctx->ws_sh_pos.p, ld_pos, j.d_w, s_pass, j.skip,  \
+                       (int64_t)0, n_steps, steps_ld, (sh_v4i *)ctx->ws_sh_A.p, d_nonint + s_base, d_meta)
+            switch (digits) {
+            case 3: LAUNCH_EXPAND(3); break;
+            case 4: LAUNCH_EXPAND(4); break;
+            case 5: LAUNCH_EXPAND(5); break;
+            case 6: LAUNCH_EXPAND(6); break;
+            default: LAUNCH_EXPAND(7); break;
+            }
 #undef LAUNCH_EXPAND
-                HIPCHK(ctx, hipGetLastError());
-            }
-            if (overlap) {
-                HIPCHK(ctx, hipEventRecord(ctx->aux_ev[1 + part], ctx->aux_stream));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1 + part], 0));
-            }
-            {
-                ProfScope ps(ctx, PK_FAST);
-                const int aligned = ((t1 - t0) / 8) * 8;                             // dealt one per XCD in turn
-                const int fill_per_xcd = ((t1 - t0 - aligned) * bpt + 7) / 8;         // blocks of the remaining tiles, spread over the XCDs
-                const unsigned nblk = (unsigned)(8 * ((aligned / 8) * bpt + fill_per_xcd));
+            HIPCHK(ctx, hipGetLastError());
+        }
+        {
+            ProfScope ps(ctx, PK_FAST);
+            const int aligned = (tiles / 8) * 8;                                 // tiles come in sets of 8, dealt one per XCD in turn
+            const int fill_per_xcd = ((tiles - aligned) * bpt + 7) / 8;           // blocks of the remaining tiles, spread over the XCDs
+            const unsigned nblk = (unsigned)(8 * ((aligned / 8) * bpt + fill_per_xcd));
 #define LAUNCH_SH(PK)                                                                                                          \
     hipLaunchKernelGGL((k_sh_mfma<PK>), dim3(nblk), dim3(256), 0, ctx->stream, p->d, p->kpitch, p->desc, (const int32_t *)d_urows,     \
-                       (const sh_v4i *)ctx->ws_sh_A.p, n_steps, steps_ld, spt, t0, t1, (int)groups, n_accgroups, bpt, aligned,          \
+                       (const sh_v4i *)ctx->ws_sh_A.p, n_steps, steps_ld, spt, 0, tiles, (int)groups, n_accgroups, bpt, aligned,        \
                        fill_per_xcd, (int *)ctx->ws_sh_partial.p, ldn)
-                if (p->packed) LAUNCH_SH(true); else LAUNCH_SH(false);
+            if (p->packed) LAUNCH_SH(true); else LAUNCH_SH(false);
 #undef LAUNCH_SH
-                HIPCHK(ctx, hipGetLastError());
-            }
+            HIPCHK(ctx, hipGetLastError());
         }
         // (the reference-order bound of a sample is a closed form of its length and its "not an integer" flag, complete once every
         // expansion of the pass has run: k_sh_finish evaluates it where it needs it)

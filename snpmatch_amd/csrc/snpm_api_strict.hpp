@@ -43,46 +43,29 @@ int launch_strict_dense(snpm_query *q, int skip, const int64_t *d_seg_off, int64
                                     REEVAL_CAP, gate ? 2 : 0, 0, dim3((unsigned)std::min<int64_t>(n_seg, 65535)),
                                     (double *)ctx->ws_seg_score.p, (uint32_t *)ctx->ws_seg_miss.p, ld);
     }
-    if (ctx->strict4) {
-        // 4 columns per lane (one dword of an int8 panel, one byte of a packed panel)
-        const int64_t lanes = (ncols + 3) / 4;
-        const int t4 = lanes >= 256 ? 256 : (lanes > 64 ? 128 : 64);
-        // a gated launch (the certificate's dense tier) usually has nothing to do: a bounded grid that walks the segments
-        dim3 grid4((unsigned)(gate ? std::min<int64_t>(n_seg, 2048) : n_seg), (unsigned)((lanes + t4 - 1) / t4));
-        ProfScope ps(ctx, PK_STRICT);
+    // 4 columns per lane (one dword of an int8 panel, one byte of a packed panel)
+    const int64_t lanes = (ncols + 3) / 4;
+    const int t4 = lanes >= 256 ? 256 : (lanes > 64 ? 128 : 64);
+    // a gated launch (the certificate's dense tier) usually has nothing to do: a bounded grid that walks the segments
+    dim3 grid4((unsigned)(gate ? std::min<int64_t>(n_seg, 2048) : n_seg), (unsigned)((lanes + t4 - 1) / t4));
+    ProfScope ps(ctx, PK_STRICT);
 #define LAUNCH_STRICT4(S, G)                                                                                     \
-    do {                                                                                                         \
-        if (p->packed)                                                                                           \
+    do {                                                                                                     \
+        if (p->packed)                                                                                       \
             hipLaunchKernelGGL((k_strict4<S, G, true>), grid4, dim3(t4), 0, ctx->stream, p->d, p->kpitch, q->d_row_idx, q->row0, \
                                q->d_w, seg_off, chunk, q->n, seg0, n_seg, ncols, (double *)ctx->ws_seg_score.p,  \
                                (uint32_t *)ctx->ws_seg_miss.p, ld, (const int *)nullptr, gate, REEVAL_CAP, p->desc); \
-        else                                                                                                     \
+        else                                                                                                 \
             hipLaunchKernelGGL((k_strict4<S, G, false>), grid4, dim3(t4), 0, ctx->stream, p->d, p->pitch, q->d_row_idx, q->row0, \
                                q->d_w, seg_off, chunk, q->n, seg0, n_seg, ncols, (double *)ctx->ws_seg_score.p,  \
                                (uint32_t *)ctx->ws_seg_miss.p, ld, (const int *)p->d_other, gate, REEVAL_CAP);   \
     } while (0)
-        if (skip) {
-            if (gather) LAUNCH_STRICT4(true, true); else LAUNCH_STRICT4(true, false);
-        } else {
-            if (gather) LAUNCH_STRICT4(false, true); else LAUNCH_STRICT4(false, false);
-        }
-#undef LAUNCH_STRICT4
-        HIPCHK(ctx, hipGetLastError());
-        return SNPM_OK;
-    }
-    const int thr = ncols > 128 ? 256 : (ncols > 64 ? 128 : 64);
-    dim3 grid((unsigned)(gate ? std::min<int64_t>(n_seg, 2048) : n_seg), (unsigned)((ncols + thr - 1) / thr));
-    ProfScope ps(ctx, PK_STRICT);
-#define LAUNCH_STRICT(S, G)                                                                                       \
-    hipLaunchKernelGGL((k_strict<S, G>), grid, dim3(thr), 0, ctx->stream, p->d, p->kpitch, p->desc, q->d_row_idx, q->row0,  \
-                       q->d_w, seg_off, chunk, q->n, seg0, n_seg, (const int32_t *)nullptr, ncols,                \
-                       (double *)ctx->ws_seg_score.p, (uint32_t *)ctx->ws_seg_miss.p, ld, gate, REEVAL_CAP)
     if (skip) {
-        if (gather) LAUNCH_STRICT(true, true); else LAUNCH_STRICT(true, false);
+        if (gather) LAUNCH_STRICT4(true, true); else LAUNCH_STRICT4(true, false);
     } else {
-        if (gather) LAUNCH_STRICT(false, true); else LAUNCH_STRICT(false, false);
+        if (gather) LAUNCH_STRICT4(false, true); else LAUNCH_STRICT4(false, false);
     }
-#undef LAUNCH_STRICT
+#undef LAUNCH_STRICT4
     HIPCHK(ctx, hipGetLastError());
     return SNPM_OK;
 }

@@ -27,13 +27,12 @@ namespace {
 // ---------------------------------------------------------------------------------------------- host thread pool
 class HostPool {
 public:
-    // Workers SPIN for a short while (SNPM_POOL_SPIN_US, default 400 us) for the next run() before they block on the condition
+    // Workers SPIN for a short while (kSpinUs) for the next run() before they block on the condition
     // variable, and so does the caller for the last task of a run: a sleeping thread takes 30-50 us to wake, which was most of
     // the 0.1 ms a 200k-SNP sample's staging fill took (snpm_genotype_once: calls follow each other within that window when
     // samples are scored in a row).  Long waits still sleep.
     explicit HostPool(int n)
     {
-        if (const char *e = getenv("SNPM_POOL_SPIN_US")) spin_us_ = atoi(e) > 0 ? atoi(e) : 0;
         for (int i = 0; i < n; ++i) threads_.emplace_back([this] { loop(); });
     }
     ~HostPool()
@@ -76,7 +75,6 @@ private:
     template <class Pred>
     bool spin_until(Pred done) const
     {
-        if (spin_us_ <= 0) return done();
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
             for (int i = 0; i < 64; ++i) {
@@ -85,7 +83,7 @@ private:
                 _mm_pause();
 #endif
             }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us_)) return done();
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kSpinUs)) return done();
         }
     }
     void work()
@@ -128,7 +126,7 @@ private:
     std::atomic<int> pending_{0};
     std::atomic<uint64_t> gen_{0};
     std::atomic<bool> stop_{false};
-    int spin_us_ = 400;
+    static constexpr int kSpinUs = 400;
 };
 
 // Copy into a pinned staging slab with non-temporal stores: the slab is read next by the DMA engine, not by this core, so the

@@ -4,25 +4,6 @@
 
 namespace snpm {
 // ------------------------------------------------------------------------------------------------
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int BPL>
-struct LoadT;
-template <>
-struct LoadT<4> { typedef uint32_t type; };
-template <>
-struct LoadT<8> { typedef u32x2 type; };
-template <>
-struct LoadT<16> { typedef u32x4 type; };
-
-__device__ __forceinline__ uint32_t dword_of(const uint32_t &v, int) { return v; }
-__device__ __forceinline__ uint32_t dword_of(const u32x2 &v, int k) { return k == 0 ? v.x : v.y; }
-__device__ __forceinline__ uint32_t dword_of(const u32x4 &v, int k)
-{
-    return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
-}
-
 // One SNP row for one lane: NDW dwords of accession bytes.
 //   address of element j of dword x = group_base | byte,  byte = (code & 3) * 8 + roff, built by ONE
 //   v_perm_b32 (group_base is 256-B aligned and wave-uniform; roff in {0,128} selects the half of the
@@ -60,17 +41,10 @@ __device__ __forceinline__ void fast_row(const uint32_t (&x)[NDW], uint32_t grou
     for (int e = 0; e < NDW * 4; ++e) acc[e] += w[e];
 }
 
-template <int BPL, bool NT>
-__device__ __forceinline__ void load_row(const int8_t *p, uint32_t (&x)[BPL / 4])
+// one dword (4 accessions) of a row per lane; panel bytes are read once: non-temporal loads (+5-8 % measured)
+__device__ __forceinline__ void load_row(const int8_t *p, uint32_t (&x)[1])
 {
-    typedef typename LoadT<BPL>::type load_t;
-    load_t v;
-    if (NT)
-        v = __builtin_nontemporal_load(reinterpret_cast<const load_t *>(p));
-    else
-        v = *reinterpret_cast<const load_t *>(p);
-#pragma unroll
-    for (int k = 0; k < BPL / 4; ++k) x[k] = dword_of(v, k);
+    x[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p));
 }
 
 // one SNP row of one lane
@@ -96,14 +70,15 @@ __device__ __forceinline__ void load_row(const int8_t *p, uint32_t (&x)[BPL / 4]
 // [part_desc[3p], part_desc[3p+1]) of the (concatenated) matched list -- never more than EPOCH_TILES tiles, all inside
 // one segment -- and writes its partial sums to slot part_desc[3p+2]; k_reduce_seg adds the slots of a segment in
 // order.  Without SEG the arguments part_desc is unused and the code is the tile-interleaved pass described above.
-template <int BPL, bool SKIP, bool GATHER, bool NT, bool SEG = false, int TR = TILE_ROWS>
-__global__ void __launch_bounds__(WAVE *MAX_WAVES_PER_BLOCK, (BPL <= 4 ? SNPM_FAST_MIN_WAVES : 1))
+template <bool SKIP, bool GATHER, bool SEG = false, int TR = TILE_ROWS>
+__global__ void __launch_bounds__(WAVE *MAX_WAVES_PER_BLOCK, SNPM_FAST_MIN_WAVES)
 k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__ row_idx, int64_t row0, int64_t n,
        const double *__restrict__ lut, double *__restrict__ out_score, uint32_t *__restrict__ out_miss, int64_t ld,
        const int64_t *__restrict__ part_desc = nullptr, int tile_rows_rt = 0)
 {
-    // BPL = bytes (= accessions = accumulators) per lane and row; packed panels have their own kernels below
-    static_assert(BPL == 4 || BPL == 8 || BPL == 16, "int8 panels: 4, 8 or 16 bytes per lane");
+    // BPL = bytes (= accessions = accumulators) per lane and row: one dword.  8 and 16 B per lane streamed at 4.4 and 5.3 TB/s
+    // against 6.5 TB/s (10k x 6.25M panel, round 1) and were removed; packed panels have their own kernels below
+    constexpr int BPL = 4;
     constexpr int NDW = BPL / 4;
     constexpr int EPL = BPL;
     // rows per prefetch group: 4 (G*32 B = half a 256-B LUT block); 8-row groups spill at the 80-VGPR budget and measured no gain
@@ -191,7 +166,7 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
         }
         uint32_t xa[G][NDW], xb[G][NDW];
 #pragma unroll
-        for (int u = 0; u < G; ++u) load_row<BPL, NT>(row_ptr(rbase + T0 * TRR + u), xa[u]);
+        for (int u = 0; u < G; ++u) load_row(row_ptr(rbase + T0 * TRR + u), xa[u]);
         __syncthreads();
 
         int buf = 0;
@@ -249,11 +224,11 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
                 const int64_t rafter = (g + 2 < TRR / G) ? rnext + G : ntr0;
                 // ---- group g (data in xa); request group g+1 into xb
 #pragma unroll
-                for (int u = 0; u < G; ++u) load_row<BPL, NT>(row_ptr(rnext + u), xb[u]);
+                for (int u = 0; u < G; ++u) load_row(row_ptr(rnext + u), xb[u]);
                 SCORE_GROUP(xa, g);
                 // ---- group g+1 (data in xb); request the following group into xa
 #pragma unroll
-                for (int u = 0; u < G; ++u) load_row<BPL, NT>(row_ptr(rafter + u), xa[u]);
+                for (int u = 0; u < G; ++u) load_row(row_ptr(rafter + u), xa[u]);
                 SCORE_GROUP(xb, g + 1);
             }
             if (g < full_groups) {                               // odd group count: only in the last tile of all
@@ -262,7 +237,7 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
 #undef SCORE_GROUP
             for (int r = full_groups * G; r < rows; ++r) {      // at most G-1 rows: last tile of all
                 uint32_t x[NDW];
-                load_row<BPL, NT>(row_ptr(tr0 + r), x);
+                load_row(row_ptr(tr0 + r), x);
                 const uint32_t group_base = lds_base + (uint32_t)(r >> 3) * 256u;
                 const uint32_t roff4 = (uint32_t)(r & 7) * 0x20202020u;        // (r & 7) * 32 in every byte
                 SCORE_ROW(0, x, group_base, roff4, (uint32_t)(r & 7) * 32u);

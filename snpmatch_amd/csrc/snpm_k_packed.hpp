@@ -53,7 +53,7 @@ static_assert(Q4_TILE_ROWS % (2 * Q4_G) == 0 && Q4_TILE_ROWS <= 127, "two regist
 // TR_: rows per tile = TR_ / 4 tables of 2 KiB in LDS.  64 for blocks of four waves and more; narrow panels run blocks of one
 // to three waves, and with 34 KiB each only four of those fit a CU (1135 accessions: 8 resident waves, 512 and fewer: 4 -- one
 // per SIMD): their tiles have 16 (one wave) or 32 rows (two, three), so that LDS stops bounding the resident waves.
-template <bool SKIP, bool GATHER, bool NT, bool SEG = false, int TR_ = Q4_TILE_ROWS>
+template <bool SKIP, bool GATHER, bool SEG = false, int TR_ = Q4_TILE_ROWS>
 __global__ void __launch_bounds__(WAVE *MAX_WAVES_PER_BLOCK, SNPM_Q4_MIN_WAVES)
 k_fast_packed_q4(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__ row_idx, int64_t row0, int64_t n,
                  const double *__restrict__ lut, double *__restrict__ out_score, uint32_t *__restrict__ out_miss, int64_t ld,
@@ -146,7 +146,7 @@ k_fast_packed_q4(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__
         uint32_t off = lane_off;
         asm volatile("" : "+v"(off));                     // keeps the saddr form of the load (see k_fast)
         const uint32_t *ptr = reinterpret_cast<const uint32_t *>(rowbase + off);
-        return NT ? __builtin_nontemporal_load(ptr) : *ptr;
+        return __builtin_nontemporal_load(ptr);
     };
     // G consecutive rows starting at matched row r: one buffer resource per group (scalar registers), the row inside the group
     // in the scalar offset, the lane's bytes in the vector offset -- no per-load vector instruction (the saddr form of
@@ -162,7 +162,7 @@ k_fast_packed_q4(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__
                 const_cast<int8_t *>(dbw + (row0 + r) * pw), 0, (int)(G * pw), 0x00020000);
 #pragma unroll
             for (int u = 0; u < G; ++u)
-                x[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rows, lane_off, (int)(u * pw), NT ? 2 : 0);
+                x[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rows, lane_off, (int)(u * pw), 2);
         } else {
 #pragma unroll
             for (int u = 0; u < G; ++u) x[u] = load(r + u);
@@ -385,7 +385,7 @@ k_fast_packed_q4(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__
                 x[u] = 0u;
                 if (on) {
                     const uint32_t *ptr = reinterpret_cast<const uint32_t *>(dbw + row_idx[tr + grp * G + u] * pw + (my_dword(ph_j) - dw0) * 4);
-                    x[u] = NT ? __builtin_nontemporal_load(ptr) : *ptr;
+                    x[u] = __builtin_nontemporal_load(ptr);
                 }
             } else {
                 x[u] = on ? load(tr + (int64_t)it * ph * G + u) : 0u;   // lane_off carries my phase's rows
@@ -516,7 +516,7 @@ k_fast_packed_q4(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__
         (L) = __builtin_amdgcn_bitop3_b32(a_, b_, c_, 0x96);                    \
     } while (0)
 
-template <bool SKIP, bool GATHER, bool NT>
+template <bool SKIP, bool GATHER>
 __global__ void __launch_bounds__(WAVE *MAX_WAVES_PER_BLOCK, 6)
 k_fast_bits(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__ row_idx, int64_t row0, int64_t n,
             const uint8_t *__restrict__ wbits, double *__restrict__ out_score, uint32_t *__restrict__ out_miss, int64_t ld,
@@ -580,7 +580,7 @@ k_fast_bits(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restr
         uint32_t off = lane_off;
         asm volatile("" : "+v"(off));
         const uint32_t *ptr = reinterpret_cast<const uint32_t *>(rowbase + off);
-        return NT ? __builtin_nontemporal_load(ptr) : *ptr;
+        return __builtin_nontemporal_load(ptr);
     };
     // H consecutive rows through a buffer resource (see k_fast_packed_q4::load_group)
     auto load_rows = [&](uint32_t (&x)[4], int64_t r) {
@@ -589,7 +589,7 @@ k_fast_bits(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restr
                 const_cast<int8_t *>(dbw + (row0 + r) * pw), 0, (int)(4 * pw), 0x00020000);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                x[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rows, lane_off, (int)(u * pw), NT ? 2 : 0);
+                x[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rows, lane_off, (int)(u * pw), 2);
         } else {
 #pragma unroll
             for (int u = 0; u < 4; ++u) x[u] = load(r + u);
@@ -781,7 +781,7 @@ k_fast_bits(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restr
                         x[u] = 0u;
                         if (on) {
                             const uint32_t *ptr = reinterpret_cast<const uint32_t *>(dbw + row_idx[tr0 + grp * 8 + u] * pw + byte0);
-                            x[u] = NT ? __builtin_nontemporal_load(ptr) : *ptr;
+                            x[u] = __builtin_nontemporal_load(ptr);
                         }
                     } else {
                         x[u] = on ? load(tr0 + (int64_t)it * ph * 8 + u) : 0u;      // lane_off carries my phase's rows

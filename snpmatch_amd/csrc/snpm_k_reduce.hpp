@@ -89,68 +89,8 @@ __global__ void k_reduce(const double *__restrict__ part_score, const uint32_t *
     if (d_eref) flag_if_uncertain(s, a, d_eref, efast, force_first, cols, count, cap);
 }
 
-// k_reduce_groups and k_reduce in ONE launch (round 5: a launch costs ~5 us of stream time, the two reduce steps of a 200k-SNP
-// sample took 10 of its 130): grid (column blocks, groups) as k_reduce_groups; every block leaves its group's sums and takes a
-// ticket of its column block, the block that draws the last ticket adds the groups in order (the additions, and therefore the
-// bits, of the two-kernel form), runs the certificate and puts the ticket back to zero.  Hand-off without cache maintenance: the
-// group sums leave as write-through (sc1) stores, the wave waits for them (vmcnt(0)), one lane takes the ticket with an agent-scope
-// atomic; the block whose ticket came last reads the sums with sc1 loads (L2-served, never a stale L1 line).
-__global__ void __launch_bounds__(64)
-k_reduce_all(const double *__restrict__ part_score, const uint32_t *__restrict__ part_miss, int64_t n_slots, int64_t ld,
-             int64_t n_acc, int64_t n_rows, double *__restrict__ grp_score, uint32_t *__restrict__ grp_miss,
-             double *__restrict__ score, int64_t *__restrict__ ninfo, const double *__restrict__ d_eref, double efast,
-             int force_first, int32_t *__restrict__ cols, int *__restrict__ count, int cap, unsigned *__restrict__ tickets)
-{
-    __shared__ int s_last;
-    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t g = blockIdx.y;
-    const int64_t n_groups = gridDim.y;
-    if (a < n_acc) {
-        const int64_t s0 = g * REDUCE_GROUP;
-        const int64_t s1 = (s0 + REDUCE_GROUP < n_slots) ? s0 + REDUCE_GROUP : n_slots;
-        double s = 0.0;
-        uint32_t m = 0;
-        int64_t k = s0;
-        for (; k + 8 <= s1; k += 8) {
-            double v[8];
-            uint32_t c[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                v[u] = part_score[(k + u) * ld + a];
-                c[u] = part_miss[(k + u) * ld + a];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                s = s + v[u];
-                m += c[u];
-            }
-        }
-        for (; k < s1; ++k) {
-            s = s + part_score[k * ld + a];
-            m += part_miss[k * ld + a];
-        }
-        // write-through stores (sc1): the sums are in memory, not in this XCD's L2, once the wave's vmcnt is zero -- no
-        // cache write-back per block (a __threadfence() here made the fused kernel slower than the two launches it replaces)
-        __hip_atomic_store(&grp_score[g * ld + a], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&grp_miss[g * ld + a], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // one wave per block: its own stores are all there is to wait for
-    if (threadIdx.x == 0)
-        s_last = (__hip_atomic_fetch_add(&tickets[blockIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(n_groups - 1)) ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) __hip_atomic_store(&tickets[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a >= n_acc) return;
-    double s = 0.0;
-    int64_t m = 0;
-    for (int64_t p = 0; p < n_groups; ++p) {
-        s = s + __hip_atomic_load(&grp_score[p * ld + a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        m += __hip_atomic_load(&grp_miss[p * ld + a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    score[a] = s;
-    ninfo[a] = n_rows - m;
-    if (d_eref) flag_if_uncertain(s, a, d_eref, efast, force_first, cols, count, cap);
-}
+// (One launch for both steps, with a ticket per column block, measured slower and was removed: 12.8 us against 5.4 + 4.7 us on a
+// 200k-SNP sample, profiles/r05_once_timeline_fused_reduce.txt.)
 
 // ------------------------------------------------------------------------------------------------
 // Jobs scored SNP slab after SNP slab (panels larger than HBM): running totals.
@@ -529,7 +469,7 @@ __device__ __forceinline__ void seg_bounds(const int64_t *__restrict__ seg_off, 
 // Re-evaluation kernels are launched before the host knows how many accessions the certificate flagged; they
 // read the count on the device and leave at once when their tier is not the one that has to run:
 //   sparse tier: 1 <= *count <= cap   (k_strict_sparse / _T, k_scan_few, k_patch)
-//   dense tier : *count > cap         (k_strict4 / k_strict, k_scan: every accession in reference order)
+//   dense tier : *count > cap         (k_strict4, k_scan: every accession in reference order)
 __device__ __forceinline__ bool dense_tier_off(const int *__restrict__ gate, int cap) { return gate && *gate <= cap; }
 
 }  // namespace snpm

@@ -1,66 +1,16 @@
-// snpm_k_strict.hpp -- reference summation order: k_strict / k_strict4 / k_strict_sparse(_T), the accession-major packed copy they read, the chains of chunk totals (k_scan, k_scan_few) and the patch of re-evaluated accessions.
+// snpm_k_strict.hpp -- reference summation order: k_strict4 / k_strict_sparse(_T), the accession-major packed copy they read, the chains of chunk totals (k_scan, k_scan_few) and the patch of re-evaluated accessions.
 // One of the kernel-family headers behind snpm_kernels.hpp (include that one: the families share constants and helpers in this order).
 #pragma once
 
 namespace snpm {
 // ------------------------------------------------------------------------------------------------
-// Strict (reference-order) segment sums.
-//   grid.x = segment, grid.y = column blocks of blockDim.x lanes
-//   cols: optional list of accession indices (NULL = dense 0..ncols-1)
-//   out_score [n_seg, ld] fp64 = ((0 + A_ref) + A_het) + A_alt, out_miss [n_seg, ld] u32
-template <bool SKIP, bool GATHER>
-__global__ void __launch_bounds__(256)
-k_strict(const int8_t *__restrict__ db, int64_t pitch, int64_t packed, const int64_t *__restrict__ row_idx, int64_t row0,
-         const double *__restrict__ w, const int64_t *__restrict__ seg_off, int64_t chunk, int64_t n, int64_t seg0,
-         int64_t n_seg, const int32_t *__restrict__ cols, int64_t ncols, double *__restrict__ out_score,
-         uint32_t *__restrict__ out_miss, int64_t ld, const int *__restrict__ gate, int gate_cap)
-{
-    if (dense_tier_off(gate, gate_cap)) return;
-    const int64_t i = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
-    if (i >= ncols) return;
-    const int64_t col = cols ? (int64_t)cols[i] : i;
-    // seg = output row (the segment itself is seg0 + seg when the pieces are implicit); a gated launch uses a
-    // bounded grid and walks the segments, so that a launch that has nothing to do costs a few microseconds
-    for (int64_t seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {
-    int64_t r0, r1;
-    seg_bounds(seg_off, chunk, n, seg_off ? seg : seg0 + seg, r0, r1);
-    double a_ref = 0.0, a_het = 0.0, a_alt = 0.0;
-    uint32_t miss = 0;
-    int64_t r = r0;
-    for (; r + 4 <= r1; r += 4) {
-        int b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t prow = GATHER ? row_idx[r + u] : (row0 + r + u);
-            b[u] = code_at(db, pitch, prow, col, packed);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double w0 = w[3 * (r + u) + 0], w1 = w[3 * (r + u) + 1], w2 = w[3 * (r + u) + 2];
-            a_ref = add_if(a_ref, b[u] == 0, w0);
-            if (!SKIP) a_het = add_if(a_het, b[u] == 2, w1);
-            a_alt = add_if(a_alt, b[u] == 1, w2);
-            miss += SKIP ? (b[u] < 0 || b[u] == 2) : (b[u] < 0);
-        }
-    }
-    for (; r < r1; ++r) {
-        const int64_t prow = GATHER ? row_idx[r] : (row0 + r);
-        const int b = code_at(db, pitch, prow, col, packed);
-        const double w0 = w[3 * r + 0], w1 = w[3 * r + 1], w2 = w[3 * r + 2];
-        a_ref = add_if(a_ref, b == 0, w0);
-        if (!SKIP) a_het = add_if(a_het, b == 2, w1);
-        a_alt = add_if(a_alt, b == 1, w2);
-        miss += SKIP ? (b < 0 || b == 2) : (b < 0);
-    }
-    out_score[seg * ld + i] = ((0.0 + a_ref) + a_het) + a_alt;
-    out_miss[seg * ld + i] = miss;
-    }
-}
-
 // Dense strict kernel: 4 adjacent accession columns per lane (int8 panel: one dword per row; packed panel: one
-// byte = four 2-bit calls), same arithmetic and order as k_strict (three sequential per-category sums per column
-// and segment).
+// byte = four 2-bit calls).  Per column and segment three sequential per-category sums over the segment's rows in row
+// order (ref, het, alt: a call adds its row's weight to the sum of its class); out_score = ((0 + A_ref) + A_het) + A_alt,
+// out_miss the count of missing calls (with SKIP: and of hets, which then add nothing).
 //   grid.x = segment, grid.y = blocks of blockDim.x lanes x 4 columns;  out_* [n_seg, ld]
+//   seg = output row (the segment itself is seg0 + seg when the pieces are implicit); a gated launch uses a
+//   bounded grid and walks the segments, so that a launch that has nothing to do costs a few microseconds
 //   MASKS: two compares per call instead of three (int8 panels whose calls are all in {0, 1, 2, missing}, and packed
 //   panels, whose row byte goes through a 256-entry table of compare-ready bits), see below.
 
@@ -90,7 +40,7 @@ strict4_segments(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__
                  int64_t n_seg, int64_t ncols, double *__restrict__ out_score, uint32_t *__restrict__ out_miss, int64_t ld,
                  int64_t c0, const uint4 *lut, uint32_t coff_sub = 0u)
 {
-    for (int64_t seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {          // one pass unless the launch is gated (see k_strict)
+    for (int64_t seg = blockIdx.x; seg < n_seg; seg += gridDim.x) {          // one pass unless the launch is gated (see above)
     int64_t r0, r1;
     seg_bounds(seg_off, chunk, n, seg_off ? seg : seg0 + seg, r0, r1);
     double a_ref[4] = {0.0, 0.0, 0.0, 0.0}, a_het[4] = {0.0, 0.0, 0.0, 0.0}, a_alt[4] = {0.0, 0.0, 0.0, 0.0};
@@ -363,7 +313,8 @@ k_strict4(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restric
 // Strict segment sums for a SHORT list of columns (the accessions SNPM_MODE_EXACT has to re-evaluate):
 // one lane per (segment, column) pair so that every lane of a wave is busy and 8 independent byte
 // loads per lane are in flight (each is its own cache line: this path is latency-bound).
-// Same arithmetic and order as k_strict.  out_* [n_seg, ld].
+// Same arithmetic and order as k_strict4 (three sequential per-category sums per column and segment, in row order).
+// out_* [n_seg, ld].
 template <bool SKIP, bool GATHER>
 __global__ void __launch_bounds__(256)
 k_strict_sparse(const int8_t *__restrict__ db, int64_t pitch, int64_t packed, const int64_t *__restrict__ row_idx,

@@ -16,7 +16,7 @@
 //              issued and waited for by hand.
 //   k_fast_bits  hard-call samples (all weights 0 or 1) on a packed panel: bit-plane boolean scoring and
 //              bit-sliced counting, no LDS, no fp64.
-//   k_strict4 / k_strict / k_strict_sparse(_T)  reference summation order (three per-category sequential fp64
+//   k_strict4 / k_strict_sparse(_T)  reference summation order (three per-category sequential fp64
 //              sums per segment, core/snpmatch.py:85-87).  Used for cross windows, for SNPM_MODE_STRICT and to
 //              re-evaluate the few accessions the fast pass cannot certify (sparse variants; _T reads the
 //              accession-major packed copy built by k_pack_transpose).
@@ -44,7 +44,7 @@
 #include "snpm_k_fast.hpp"        // k_fast
 #include "snpm_k_packed.hpp"      // k_fast_packed_q4, k_fast_bits
 #include "snpm_k_reduce.hpp"      // k_reduce*, k_carry_*, k_eseg_*, k_reduce_seg, k_strict_pairs, k_scan_pairs, k_tot_seg, helpers
-#include "snpm_k_strict.hpp"      // k_strict, k_strict4, k_strict_sparse(_T), k_pack_transpose*, k_scan, k_scan_few, k_seg_pack, k_patch
+#include "snpm_k_strict.hpp"      // k_strict4, k_strict_sparse(_T), k_pack_transpose*, k_scan, k_scan_few, k_seg_pack, k_patch
 #include "snpm_k_shared.hpp"      // k_sh_*: the shared-row scan of a batch (int8 MFMA contraction of fixed-point weight digits with the one-hot panel)
 #include "snpm_k_post.hpp"        // k_likelihood, k_binom_identity, k_segregating, k_f1_*, k_once_pack
 #include "snpm_k_io.hpp"          // k_pack_rows, k_repitch_canon, k_unpack_rows, k_synth*, k_calib_read

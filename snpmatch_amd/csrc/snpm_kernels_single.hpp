@@ -8,7 +8,7 @@
 // positions matter), then score = ((0 + A_ref) + A_het) + A_alt as everywhere else.  Pinned by the reference-generated
 // goldens tests/golden/g1b_single_acc.npz and g2b_g5b_single_acc.npz.
 //
-// k_strict_single stands in for k_strict4 / k_strict / k_strict_sparse(_T) / k_strict_pairs on such panels (the host
+// k_strict_single stands in for k_strict4 / k_strict_sparse(_T) / k_strict_pairs on such panels (the host
 // switches on snpm_panel::n_acc_total == 1: the width of the panel the REFERENCE would see, not of a rank's shard).
 // One 256-thread block per matchGTsAccs call; an edge case, written for clarity and exactness, not for bandwidth.
 #pragma once

@@ -6,13 +6,18 @@
 // 0.55-0.7 ms per 200k-SNP sample around 0.06 ms of scoring (profiles/r04_real_panel_*).  Two forms live here:
 //   genotype_once_fused (default)  the host thread pool gathers wei[sample_idx[i]] / the weight codes and the row list into ONE
 //      pinned slab, collecting the weight properties the kernels are chosen by on the way; k_once_prep reads the slab where it
-//      lies (or what the copy engine brought behind the fill) and prepares everything the scoring needs in one launch; fast pass,
+//      lies and prepares everything the scoring needs in one launch; fast pass,
 //      reduce + certificate, the sparse tier, k_once_finish (likelihood / nanmin / ratio of the truncated counts, :96, :106-117,
 //      + status) written straight into the slab: seven launches, one synchronisation.
 //   genotype_once_impl's own body (SNPM_ONCE_FUSED=0, chunk > ONCE_MAX_CHUNK, n == 0)  the first version: the slab goes up in
 //      pieces behind the fill, row check / code expansion / LUT / error bound / tiers / likelihood as separate launches of the
 //      query path, one packed copy back.
 // Both return the same bits (tests/test_gpu_once.py).
+// Switches: SNPM_ONCE_FUSED=0 (the first version's body for every call), SNPM_ONCE_TAIL=0 (k_scan_few + k_once_finish instead of
+// k_once_tail), SNPM_ONCE_TRACE (host-side times of a call on stderr).  Removed, measured slower: SNPM_ONCE_ZEROCOPY=0 (the fused
+// form's slab through the copy engine: fp64 samples 0.37-0.38 ms against 0.33-0.35 ms in place, profiles/r04_once_forms.txt) and
+// SNPM_FUSED_REDUCE=1 (one reduce launch with tickets: 12.8 us against 5.4 + 4.7 us,
+// profiles/r05_once_timeline_fused_reduce.txt); SNPM_ONCE_PIECE_TASKS is the constant 25 now.
 // Included by snpm_api.hip inside its extern "C" block.
 
 namespace {
@@ -57,7 +62,8 @@ static int once_set_table(snpm_ctx *ctx, const double *table, int64_t table_len)
 // ---- the short form of the call (default; SNPM_ONCE_FUSED=0 or a chunk above ONCE_MAX_CHUNK take genotype_once_impl's body) ----
 // GPU timeline of a coded 200k-SNP sample before: 2 copies up (67 us with their gaps), 15 kernels and fills of ~4.8 us each around
 // the 53 us of k_fast, 1 copy back = 224 us (profiles/r04_once_timeline_before.txt).  Here: the slab stays in pinned host memory
-// and k_once_prep reads it over the bus while it expands it (SNPM_ONCE_ZEROCOPY=0: staged through the copy engine as before),
+// and k_once_prep reads it over the bus while it expands it (fp64 samples too: 6.4 MB per 200k SNPs read in place 0.33-0.35 ms,
+// through the copy engine 0.37-0.38),
 // k_fast, two reduce kernels, the sparse tier (its patch inside k_scan_few), k_once_finish writing into the pinned slab:
 // 7 launches, no copy.  The > REEVAL_CAP tier runs only when the count that comes back says so (second round trip, rare).
 // Coded samples: the weight properties come from two small per-code tables (a flag byte, |entry|) made once per weight table.
@@ -70,7 +76,6 @@ static int genotype_once_fused(snpm_panel *p, const int64_t *row_idx, const doub
     const size_t na = (size_t)p->n_acc;
     const int skip = skip_hets ? 1 : 0;
     static const bool trace = getenv("SNPM_ONCE_TRACE") != nullptr;
-    const bool zero_copy = ctx->once_zero_copy != 0;        // (fp64 samples too: 6.4 MB per 200k SNPs read in place 0.33-0.35 ms, through the copy engine 0.37-0.38)
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_begin = trace ? now() : 0.0;
     snpm_query *q = nullptr;
@@ -158,49 +163,7 @@ static int genotype_once_fused(snpm_panel *p, const int64_t *row_idx, const doub
         props[(size_t)t] = pr;
     };
     if (n_wei == 0) return set_err(ctx, SNPM_ERR_BADARG, "please provide same number of positions for both sample and db");
-    // through the copy engine (SNPM_ONCE_ZEROCOPY=0): the slab goes up in pieces BEHIND the fill -- task 0 of the pool run waits,
-    // in order, for the fill tasks of each piece and enqueues its two copies -- into the query's own arrays (fp64: k_once_prep
-    // then works in place) or a staging pair (coded)
-    int32_t *d_rows32 = nullptr;
-    uint16_t *d_codes = nullptr;
-    if (!zero_copy && coded)
-        if (query_alloc(q, (void **)&d_rows32, row_bytes) != hipSuccess || query_alloc(q, (void **)&d_codes, wei_bytes + 8) != hipSuccess)
-            return set_err(ctx, SNPM_ERR_OOM, "query allocation failed");
-    const int tasks_per_piece = std::max(1, (n_tasks + 1) / 2);             // two pieces: every copy costs ~25 us of its own
-    const int n_pieces = (n_tasks + tasks_per_piece - 1) / tasks_per_piece;
-    std::vector<std::atomic<int>> piece_done((size_t)std::max(n_pieces, 1));
-    for (auto &c : piece_done) c.store(0, std::memory_order_relaxed);
-    std::atomic<int> upload_error{0};
-    auto upload_piece = [&](int k) -> bool {
-        const int64_t i0 = (int64_t)k * tasks_per_piece * piece, i1 = std::min<int64_t>(n, i0 + (int64_t)tasks_per_piece * piece);
-        if (coded)
-            return hipMemcpyAsync(d_rows32 + i0, h_rows32 + i0, (size_t)(i1 - i0) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-                   hipMemcpyAsync(d_codes + 3 * i0, h_codes + 3 * i0, (size_t)(i1 - i0) * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-        return hipMemcpyAsync(q->d_row_idx + i0, h_rows + i0, (size_t)(i1 - i0) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-               hipMemcpyAsync(q->d_w + 3 * i0, h_wei + 3 * i0, (size_t)(i1 - i0) * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    };
-    const bool overlapped = !zero_copy && pool->size() > 0 && n_pieces > 1;
-    if (overlapped) {
-        pool->run(n_tasks + 1, [&](int t) {
-            if (t == 0) {                                          // the uploader
-                if (hipSetDevice(ctx->device) != hipSuccess) { upload_error.store(1); return; }
-                for (int k = 0; k < n_pieces; ++k) {
-                    const int need = std::min(tasks_per_piece, n_tasks - k * tasks_per_piece);
-                    while (piece_done[(size_t)k].load(std::memory_order_acquire) < need) {
-#if defined(__x86_64__)
-                        _mm_pause();
-#endif
-                    }
-                    if (!upload_piece(k)) { upload_error.store(1); return; }
-                }
-                return;
-            }
-            fill(t - 1);
-            piece_done[(size_t)((t - 1) / tasks_per_piece)].fetch_add(1, std::memory_order_release);
-        });
-    } else {
-        pool->run(n_tasks, fill);
-    }
+    pool->run(n_tasks, fill);
     const double t_filled = trace ? now() : 0.0;
     long double tot = 0;
     int flags = 0;
@@ -219,29 +182,15 @@ static int genotype_once_fused(snpm_panel *p, const int64_t *row_idx, const doub
             }
         }
     }
-    if (bad_at >= 0 || (flags & 4) || upload_error.load()) {
-        if (!zero_copy) (void)hipStreamSynchronize(ctx->stream);   // pieces already on their way read the slab
-        if (bad_at >= 0)
-            return set_err(ctx, SNPM_ERR_BADARG, "row index %lld at %lld outside the panel (n_snp %lld), or a sample index / weight code outside the weights",
-                           (long long)row_idx[bad_at], (long long)bad_at, (long long)n_snp);
-        if (flags & 4) return set_err(ctx, SNPM_ERR_BADARG, "SNP weights must be finite (a NaN or infinite weight was given)");
-        return set_err(ctx, SNPM_ERR_HIP, "upload of the sample failed");
-    }
+    if (bad_at >= 0)
+        return set_err(ctx, SNPM_ERR_BADARG, "row index %lld at %lld outside the panel (n_snp %lld), or a sample index / weight code outside the weights",
+                       (long long)row_idx[bad_at], (long long)bad_at, (long long)n_snp);
+    if (flags & 4) return set_err(ctx, SNPM_ERR_BADARG, "SNP weights must be finite (a NaN or infinite weight was given)");
 
-    // ---- prep: one launch (reads the pinned slab in place, or what the copy engine has brought)
-    const void *src_rows = h_slab, *src_wei = h_slab + row_bytes;
-    if (zero_copy) {
-        void *dp = nullptr;
-        HIPCHK(ctx, hipHostGetDevicePointer(&dp, h_slab, 0));
-        src_rows = dp;
-        src_wei = (const char *)dp + row_bytes;
-    } else {
-        if (!overlapped)
-            for (int k = 0; k < n_pieces; ++k)
-                if (!upload_piece(k)) return set_err(ctx, SNPM_ERR_HIP, "upload of the sample failed");
-        src_rows = coded ? (const void *)d_rows32 : (const void *)q->d_row_idx;
-        src_wei = coded ? (const void *)d_codes : (const void *)q->d_w;
-    }
+    // ---- prep: one launch (reads the pinned slab in place)
+    void *d_slab = nullptr;
+    HIPCHK(ctx, hipHostGetDevicePointer(&d_slab, h_slab, 0));
+    const void *src_rows = d_slab, *src_wei = (const char *)d_slab + row_bytes;
     const int64_t K = (n + chunk - 1) / chunk;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(K, 2048));
     if ((rc = ensure(ctx, ctx->ws_epart, (size_t)grid * sizeof(double)))) return rc;
@@ -285,15 +234,7 @@ static int genotype_once_fused(snpm_panel *p, const int64_t *row_idx, const doub
     }
     if ((rc = ensure(ctx, ctx->ws_lik_l, na * sizeof(double)))) return rc;
     int64_t *h_out = (int64_t *)h_slab;
-    int64_t *d_out = h_out;
-    if (zero_copy) {
-        void *dp = nullptr;
-        HIPCHK(ctx, hipHostGetDevicePointer(&dp, h_slab, 0));
-        d_out = (int64_t *)dp;
-    } else {
-        if ((rc = ensure(ctx, ctx->ws_once, out_words * sizeof(int64_t)))) return rc;
-        d_out = (int64_t *)ctx->ws_once.p;
-    }
+    int64_t *d_out = (int64_t *)d_slab;                 // the results are written straight into the slab
     // the sparse tier behind the fast pass; its chain kernel also does the likelihood / ratio / status step (k_once_tail)
     bool tail_done = false;
     if (certified) {
@@ -302,17 +243,13 @@ static int genotype_once_fused(snpm_panel *p, const int64_t *row_idx, const doub
         tail.state = (unsigned *)ctx->ws_once_state.p; tail.lik_tmp = (double *)ctx->ws_lik_l.p; tail.out = d_out;
         const bool fuse = ctx->once_tail && !single_accession(p);
         if ((rc = enqueue_reevaluation(q, skip, chunk, false, fuse ? &tail : nullptr))) return rc;
-        if (fuse) {
-            if (!zero_copy) HIPCHK(ctx, hipMemcpyAsync(h_out, d_out, out_words * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-            tail_done = true;
-        }
+        tail_done = fuse;
     }
     auto finish = [&]() -> int {
         hipLaunchKernelGGL(k_once_finish, dim3(1), dim3(1024), 0, ctx->stream, (const double *)q->d_score, (const int64_t *)q->d_ninfo, (int64_t)na,
                            lik ? 1 : 0, certified ? (const int *)q->cert_count() : (const int *)nullptr, (unsigned *)ctx->ws_once_state.p,
                            (double *)ctx->ws_lik_l.p, d_out);
         HIPCHK(ctx, hipGetLastError());
-        if (!zero_copy) HIPCHK(ctx, hipMemcpyAsync(h_out, d_out, out_words * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         return SNPM_OK;
     };
     if (!tail_done && (rc = finish())) return rc;
@@ -332,8 +269,8 @@ static int genotype_once_fused(snpm_panel *p, const int64_t *row_idx, const doub
         n_flag = h_out[4 * na];
     }
     if (trace)
-        fprintf(stderr, "[snpm once] n %lld: fill %.3f ms (%d tasks), enqueue %.3f ms, wait %.3f ms (fused%s)\n", (long long)n, t_filled - t_begin,
-                n_tasks, t_enqueued - t_filled, now() - t_enqueued, zero_copy ? ", zero-copy" : "");
+        fprintf(stderr, "[snpm once] n %lld: fill %.3f ms (%d tasks), enqueue %.3f ms, wait %.3f ms (fused)\n", (long long)n, t_filled - t_begin,
+                n_tasks, t_enqueued - t_filled, now() - t_enqueued);
     if (h_out[4 * na + 1] & 1) return set_err(ctx, SNPM_ERR_DOMAIN, "provided y is greater than n");       // core/snpmatch.py:43
     memcpy(score, h_out, na * sizeof(double));
     memcpy(ninfo, h_out + na, na * sizeof(int64_t));
@@ -490,9 +427,9 @@ static int genotype_once_impl(snpm_panel *p, const int64_t *row_idx, const doubl
     // The slab goes up BEHIND the fill: task 0 of the pool run is the uploader -- it waits (in order) for the fill tasks of each
     // piece and enqueues that piece's two copies, while the other threads keep filling.  Without pool threads the
     // calling thread fills everything first.
-    static const int kTasksPerPiece = std::max(1, getenv("SNPM_ONCE_PIECE_TASKS") ? atoi(getenv("SNPM_ONCE_PIECE_TASKS")) : 25);   // x 4096 rows: a 200k-SNP sample
-                                                                                   // goes up in two pieces (every copy costs ~25 us on its own:
-                                                                                   // 13 pieces 0.38 ms, 2 pieces 0.19 ms, 1 piece 0.21 ms of GPU-side wait)
+    // x 4096 rows: a 200k-SNP sample goes up in two pieces (every copy costs ~25 us on its own: 13 pieces 0.38 ms, 2 pieces 0.19 ms,
+    // 1 piece 0.21 ms of GPU-side wait)
+    constexpr int kTasksPerPiece = 25;
     const int n_pieces = (n_tasks + kTasksPerPiece - 1) / kTasksPerPiece;
     std::vector<std::atomic<int>> piece_done((size_t)std::max(n_pieces, 1));
     for (auto &c : piece_done) c.store(0, std::memory_order_relaxed);

@@ -210,10 +210,9 @@ def _ctx_with(**env):
 
 
 def test_fused_and_unfused_forms_of_the_call_agree():
-    """the short form of snpm_genotype_once (k_once_prep + k_once_finish; by default the sample is read in place from the pinned
-    slab), the same with the sample sent through the copy engine behind the fill, and the first version's kernels and copies
-    return the same bits -- plain and coded,
-    with forced sparse-tier and dense-tier re-evaluations, and with a chunk above the fused form's limit"""
+    """the short form of snpm_genotype_once (k_once_prep + k_once_finish; the sample is read in place from the pinned slab), the
+    same with the chain kernel and the finish kernel apart, and the first version's kernels and copies return the same bits --
+    plain and coded, with forced sparse-tier and dense-tier re-evaluations, and with a chunk above the fused form's limit"""
     from snpmatch_amd.core import parsers
     rng = np.random.default_rng(2024)
     n_snp, n_acc, n_in, n_match = 40000, 300, 30000, 21001
@@ -229,11 +228,10 @@ def test_fused_and_unfused_forms_of_the_call_agree():
     rows = np.sort(rng.choice(n_snp, size=n_match, replace=False)).astype(np.int64)
     sidx = np.sort(rng.choice(n_in, size=n_match, replace=False)).astype(np.int64)
     for reeval in (0, 3, 100):                     # 100 > the sparse tier's 64: the deferred dense tier
-        forms = {"fused": _ctx_with(SNPM_DEBUG_REEVAL=reeval), "copies": _ctx_with(SNPM_DEBUG_REEVAL=reeval, SNPM_ONCE_ZEROCOPY=0),
-                 "in-place": _ctx_with(SNPM_DEBUG_REEVAL=reeval, SNPM_ONCE_ZEROCOPY=1),
+        forms = {"fused": _ctx_with(SNPM_DEBUG_REEVAL=reeval),
                  "unfused": _ctx_with(SNPM_DEBUG_REEVAL=reeval, SNPM_ONCE_FUSED=0),
-                 # round 4's launch chain: two reduce launches, chain kernel and finish kernel apart (round 5 fused each pair)
-                 "seven-launches": _ctx_with(SNPM_DEBUG_REEVAL=reeval, SNPM_FUSED_REDUCE=0, SNPM_ONCE_TAIL=0)}
+                 # round 4's launch chain: chain kernel and finish kernel apart (round 5 fused the pair)
+                 "seven-launches": _ctx_with(SNPM_DEBUG_REEVAL=reeval, SNPM_ONCE_TAIL=0)}
         res = {}
         for name, c in forms.items():
             for packed in (False, True):

@@ -287,10 +287,10 @@ def test_coded_batch_through_the_shared_rows():
     ctx.close()
 
 
-def test_parts_on_two_streams_and_the_probe_agree_with_one_stream():
-    """the pass cut into parts (digit layout on the auxiliary stream beside the previous part's contraction) returns the bits of
-    the one-stream pass, over several passes over groups too; the automatic policy's probe declines scattered marker sets before
-    the full pass and lets a batch on one marker set through"""
+def test_tile_counts_and_several_passes_agree_and_the_probe_declines_scattered_markers():
+    """the pass with 32 row tiles, the same again, and with 64 row tiles in several passes over groups of samples (a 4 MB digit
+    matrix) return the same bits, back to back; the automatic policy's probe declines scattered marker sets before the full pass
+    and lets a batch on one marker set through"""
     import torch
     rng = np.random.default_rng(12)
     n_snp, n_acc = 60_000, 900
@@ -298,8 +298,8 @@ def test_parts_on_two_streams_and_the_probe_agree_with_one_stream():
     samples = chip_samples(rng, db, 40, 9000)
     off = np.concatenate([[0], np.cumsum([len(r) for r, _ in samples])]).astype(np.int64)
     res = {}
-    for name, env in (("one stream", {"SNPM_SHARED_PARTS": 1, "SNPM_SHARED_TILES": 32}), ("four parts", {"SNPM_SHARED_PARTS": 4, "SNPM_SHARED_TILES": 32}),
-                      ("eight parts, several passes", {"SNPM_SHARED_PARTS": 8, "SNPM_SHARED_TILES": 64, "SNPM_SHARED_WS_MB": 4})):
+    for name, env in (("32 tiles", {"SNPM_SHARED_TILES": 32}), ("32 tiles again", {"SNPM_SHARED_TILES": 32}),
+                      ("64 tiles, several passes", {"SNPM_SHARED_TILES": 64, "SNPM_SHARED_WS_MB": 4})):
         ctx = make_ctx(**env)
         panel = engine.Panel.from_host(ctx, db, packed=True)
         d_rows = torch.as_tensor(np.concatenate([r for r, _ in samples]), device="cuda:0")
@@ -312,10 +312,10 @@ def test_parts_on_two_streams_and_the_probe_agree_with_one_stream():
             assert st["passes"] >= 2, st
         res[name] = got
         ctx.close()
-    check_against_oracle(db, samples, res["one stream"], False)
+    check_against_oracle(db, samples, res["32 tiles"], False)
     for name, got in res.items():
         for k in ("score", "ninfo", "lik", "lrt"):
-            assert np.array_equal(np.ascontiguousarray(got[k]).view(np.uint64), np.ascontiguousarray(res["one stream"][k]).view(np.uint64)), (name, k)
+            assert np.array_equal(np.ascontiguousarray(got[k]).view(np.uint64), np.ascontiguousarray(res["32 tiles"][k]).view(np.uint64)), (name, k)
     # scattered markers: declined by the probe (the estimate is reported), same results from the per-sample pass
     ctx = make_ctx()
     panel = engine.Panel.from_host(ctx, db, packed=True)

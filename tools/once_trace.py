@@ -1,5 +1,5 @@
-"""phases of snpm_genotype_once[_coded] (SNPM_ONCE_TRACE) on 1135 x 11M int8, one 200k-SNP sample, in its three forms:
-fused + zero-copy (default for coded samples), fused + copies, the first version's kernels and copies (SNPM_ONCE_FUSED=0)"""
+"""phases of snpm_genotype_once[_coded] (SNPM_ONCE_TRACE) on 1135 x 11M int8, one 200k-SNP sample, in its two forms:
+fused (default: the sample is read in place from the pinned slab), the first version's kernels and copies (SNPM_ONCE_FUSED=0)"""
 import sys, time, os, numpy as np
 sys.path.insert(0, '.')
 os.environ["SNPM_ONCE_TRACE"] = "1"
@@ -13,7 +13,7 @@ sidx = np.sort(rng.choice(n_in, size=n, replace=False)).astype(np.int64)
 wall = np.zeros((n_in, 3)); wall[sidx] = wei
 tab = np.concatenate([engine.pl_table(256), [0.0]])
 codes = engine.weight_codes(wall, tab)
-forms = [("default", {}), ("zero-copy", {"SNPM_ONCE_ZEROCOPY": "1"}), ("copies", {"SNPM_ONCE_ZEROCOPY": "0"}), ("unfused", {"SNPM_ONCE_FUSED": "0"})]
+forms = [("default", {}), ("unfused", {"SNPM_ONCE_FUSED": "0"})]
 only = os.environ.get("ONCE_FORMS") or (sys.argv[1] if len(sys.argv) > 1 else None)      # (rocprofv3 takes the program itself after --: the selection as an argument)
 for name, env in forms:
     if only and name not in only.split(","):
