@@ -431,6 +431,23 @@ int snpm_profile_reset(snpm_ctx *ctx);
 /* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut".  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
+/* ---------------------------------------------------------------- genotype_cross */
+/* GenotypeCross.genotype_cross (core/genotype_cross.py:210-241 of the reference: a Python loop over windows x samples around
+   getWindowGenotype, :21-49) as ONE device call.  Host pointers in and out.
+     gt_codes [n, ld]  call codes (as snpm_vcf_parse_calls produces them) of every sample at the n matched segregating markers,
+                       markers in window order, the samples of a marker contiguous, ld >= n_samples
+     p1, p2 [n]        the two parents' calls (0 / 1 / 2, different at every marker)
+     win_off [n_win+1] marker range of every window: 0 = win_off[0] <= ... <= win_off[n_win] = n
+   Per (window, sample): the governing separator is the one of the window's FIRST marker of that sample (parseGT, core/parsers.py:
+   12-35); an element's value is {0, 1, 2, -1, 0}[class] under that separator and 0 under the other one; m1 = #(value == p1),
+   mh = #(value == 2), m2 = #(value == p2), tot = markers of the window; the decision is getWindowGenotype's (fp64 likeliTest).
+     geno [n_win, n_samples]        -1 'NA', 0 parent 1, 1 heterozygous, 2 parent 2
+     counts [n_win, n_samples, 3]   m1, mh, m2 (exact int32); NULL to skip
+   Every argument is validated on the host before the context or the device is touched (SNPM_ERR_BADARG with a message; with ctx ==
+   NULL the message is in snpm_last_error(NULL)); n == 0, n_win == 0 or n_samples == 0 return without a launch. */
+int snpm_cross_calls(snpm_ctx *ctx, const uint8_t *gt_codes, int64_t n, int n_samples, int64_t ld, const int8_t *p1, const int8_t *p2,
+                     const int64_t *win_off, int n_win, double lr_thres, int n_marker_thres, int8_t *geno, int32_t *counts);
+
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in
    the reference) extracts for sample column `sample_index`: CHROM, POS, the GT text as written, the first three
@@ -450,6 +467,14 @@ int snpm_vcf_fill(const snpm_vcf *vcf, char *chr, int64_t *pos, char *gt, double
 int snpm_vcf_fill_u32(const snpm_vcf *vcf, uint32_t *chr, int64_t *pos, uint32_t *gt, double *pl, int64_t *dp, uint8_t *called);
 const char *snpm_vcf_sample_name(const snpm_vcf *vcf, int i);
 int snpm_vcf_free(snpm_vcf *vcf);
+/* The same single pass for EVERY sample column (genotype_cross reads a multi-sample VCF of F2 individuals): per record CHROM, POS
+   and one call code per sample -- bits 0-2 the class (0 '0s0', 1 '1s1', 2 '0s1' / '1s0', 3 '.s.', 4 any other text with a
+   separator s), bit 3 set when s is '|', 0xFF for a genotype without a separator -- instead of the GT text.  Declines
+   (SNPM_ERR_STATE) where snpm_vcf_parse does, and when a record does not carry exactly the header's sample columns.  Sizes through
+   snpm_vcf_dims (n_records, chr_width, n_samples); snpm_vcf_fill_calls writes chr [n * chr_width] as UTF-32, pos [n] and
+   codes [n, ld] (ld >= n_samples, the samples of a record contiguous; bytes past n_samples are left alone). */
+int snpm_vcf_parse_calls(const char *path, snpm_vcf **out);
+int snpm_vcf_fill_calls(const snpm_vcf *vcf, uint32_t *chr, int64_t *pos, uint8_t *codes, int64_t ld);
 
 /* ---------------------------------------------------------------- DB input: the reference's HDF5 files (host only, no GPU) */
 /* A reader for the files the reference keeps its DBs in -- `snps` int8 [num_snps, num_accessions] in lzf chunks of (1000,

@@ -47,6 +47,7 @@ SYMBOLS = [
     "snpm_group_transport",
     "snpm_h5_open", "snpm_h5_close", "snpm_h5_last_error", "snpm_h5_list", "snpm_h5_info", "snpm_h5_attr_name", "snpm_h5_read",
     "snpm_h5_read_rows", "snpm_panel_load_h5",
+    "snpm_cross_calls", "snpm_vcf_parse_calls", "snpm_vcf_fill_calls",
 ]
 
 _lib = None
@@ -231,6 +232,9 @@ def load():
     lib.snpm_vcf_sample_name.argtypes = [p, ci]
     lib.snpm_vcf_sample_name.restype = C.c_char_p
     lib.snpm_vcf_free.argtypes = [p]
+    lib.snpm_vcf_parse_calls.argtypes = [C.c_char_p, pp]
+    lib.snpm_vcf_fill_calls.argtypes = [p, p, p, p, i64]
+    lib.snpm_cross_calls.argtypes = [p, p, i64, ci, i64, p, p, p, ci, dbl, ci, p, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]
     lib.snpm_profile_enable.argtypes = [p, ci]
     lib.snpm_profile_reset.argtypes = [p]
@@ -335,6 +339,33 @@ def vcf_parse(path, sample_index=0):
         lib.snpm_vcf_free(h)
     return {"chr": chrom, "pos": pos, "gt": gt, "pl": pl, "dp": dp, "names": names, "called": called,
             "has_gt": bool(flags.value & 1), "has_pl": bool(flags.value & 2), "has_dp": bool(flags.value & 4)}
+
+
+def vcf_parse_calls(path):
+    """native reader of EVERY sample column as call codes (snpm_vcf_parse_calls): dict with chr, pos, codes uint8 [n, n_samples]
+    and the sample names; None when the library declines the file (the caller then uses the Python reader)"""
+    lib = load()
+    h = C.c_void_p()
+    rc = lib.snpm_vcf_parse_calls(os.fsencode(path), C.byref(h))
+    if rc == SNPM_ERR_STATE:
+        return None
+    if rc != SNPM_OK:
+        raise IOError("cannot read %s" % path)
+    try:
+        n, cw, flags, ns = C.c_int64(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        lib.snpm_vcf_dims(h, C.byref(n), C.byref(cw), None, C.byref(flags), C.byref(ns))
+        n, ns = n.value, ns.value
+        chrom = np.empty(n, dtype="<U%d" % cw.value)
+        pos = np.empty(n, dtype=np.int64)
+        codes = np.empty((n, ns), dtype=np.uint8)
+        rc = lib.snpm_vcf_fill_calls(h, ptr(chrom), ptr(pos), ptr(codes), ns)
+        if rc == SNPM_ERR_STATE:          # CHROM text that is not ASCII
+            return None
+        assert rc == SNPM_OK
+        names = [lib.snpm_vcf_sample_name(h, i).decode() for i in range(ns)]
+    finally:
+        lib.snpm_vcf_free(h)
+    return {"chr": chrom, "pos": pos, "codes": codes, "names": names, "has_gt": bool(flags.value & 1)}
 
 
 def pack_rows_host(snps):

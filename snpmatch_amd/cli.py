@@ -1,8 +1,10 @@
 """
-Command line: ``snpmatch inbred`` and ``snpmatch cross`` with the reference's flags
-(snpmatch/__init__.py:44-63), logging setup (:23-34) and exit codes (:155-183), plus ``makedb-native``
-to write the flat panel format this engine streams to the GPU.  The other reference subcommands
-(genotype_cross, parser, pairsnp, makedb, simulate) are outside the accelerated path.
+Command line: ``snpmatch inbred``, ``snpmatch cross`` and ``snpmatch genotype_cross`` with the reference's flags
+(snpmatch/__init__.py:44-78), logging setup (:23-34) and exit codes (:155-183), plus ``makedb-native``
+to write the flat panel format this engine streams to the GPU.  ``genotype_cross`` serves the windowed likelihood-ratio
+mode with the parents named as two accessions of the database (``-p 6091x6191``); ``--hmm`` and ``-q / --father`` are
+refused with a message (core/genotype_cross.py says why).  The other reference subcommands (parser, pairsnp, makedb,
+simulate) are outside the accelerated path.
 """
 import argparse
 import logging
@@ -54,6 +56,18 @@ def snpmatch_cross(args):
     csmatch.potatoCrossIdentifier(args)
 
 
+def snpmatch_genotype_cross(args):
+    from .core import genotype_cross
+    if args['hmm']:
+        die(genotype_cross.HMM_REFUSED)
+    if args['father'] is not None:
+        die(genotype_cross.FATHER_REFUSED)
+    check_file(args['inFile'])
+    if not args['parents']:
+        die("parents not specified: -p 6091x6191")
+    genotype_cross.potatoCrossGenotyper(args)
+
+
 def makedb_native(args):
     """<db>.npz (snps, accessions, positions, chrs, chr_regions) or HDF5 -> <out>.snpm flat panel"""
     from .core import snp_genotype
@@ -101,6 +115,26 @@ def get_options(description, version_message):
     cross.add_argument("--genome", dest="genome", default="athaliana_tair10",
                        help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
     cross.set_defaults(func=snpmatch_cross)
+
+    gcross = sub.add_parser('genotype_cross', help="Genotype F2 individuals of a cross: parent 1 / heterozygous / parent 2 per genome window")
+    gcross.add_argument("-i", "--input_file", dest="inFile", help="multi-sample VCF file of the F2 individuals")
+    gcross.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File",
+                        help="Path to SNP matrix: native flat panel directory (.snpm), .npz, or HDF5 chunked row-wise")
+    gcross.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile",
+                        help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    gcross.add_argument("-p", "--parents", dest="parents", help="Parents of the cross as two accessions of the database: 6091x6191")
+    gcross.add_argument("-q", "--father", dest="father", default=None,
+                        help="(refused) the reference's two-VCF form of naming the parents")
+    gcross.add_argument("-b", "--binLength", dest="binLen", help="bin length", default=200000, type=int)
+    gcross.add_argument("--genome", dest="genome", default="athaliana_tair10",
+                        help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen, optionally recomb_rates)")
+    gcross.add_argument("--lr_thres", dest="lr_thres", default=1.5, type=float,
+                        help="likelihood ratio a parental call must reach over the next best class")
+    gcross.add_argument("--good_samples", dest="good_samples", default=None, help="accepted and unused, as in the reference's own call path")
+    gcross.add_argument("--hmm", action="store_true", dest="hmm", default=False, help="(refused) the reference's HMM genotyper")
+    gcross.add_argument("-o", "--output", dest="outFile", default="genotype_cross", help="output file")
+    gcross.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    gcross.set_defaults(func=snpmatch_genotype_cross)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

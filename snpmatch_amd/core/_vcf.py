@@ -64,7 +64,62 @@ def _read_calls_native(path, sample):
     }
 
 
+def read_call_codes(path, native=True):
+    """every sample column as call codes (``parsers.gt_call_code``): dict with samples, has_gt, chr, pos, codes uint8 [n, s].
+    ``native``: the library's single-pass reader first (``snpm_vcf_parse_calls``); the loop below is the generic path and the
+    definition -- a sample column a record lacks, or a FORMAT without GT, reads './.' as in ``read_calls``."""
+    if native:
+        from .. import _lib
+        raw = _lib.vcf_parse_calls(path)
+        if raw is not None:
+            return {"samples": np.array(raw["names"], dtype="U"), "has_gt": raw["has_gt"] or len(raw["pos"]) == 0,
+                    "chr": raw["chr"], "pos": raw["pos"], "codes": raw["codes"]}
+    from .parsers import gt_call_code
+    names, chrom, pos, rows = [], [], [], []
+    any_gt = False
+    known = {}                                   # genotype text -> code: a file holds a handful of distinct texts
+    missing = gt_call_code("./.")
+    with _open(path) as fh:
+        for line in fh:
+            if line.startswith("#"):
+                if line.startswith("#CHROM"):
+                    names = line.rstrip("\n").split("\t")[9:]
+                continue
+            rec = line.rstrip("\n").split("\t")
+            if len(rec) < 8:
+                continue
+            chrom.append(rec[0])
+            pos.append(int(rec[1]))
+            keys = rec[8].split(":") if len(rec) > 8 else []
+            any_gt |= "GT" in keys
+            row = bytearray([missing]) * len(names)
+            for s in range(min(len(names), len(rec) - 9)):
+                g = _sample_fields(keys, rec[9 + s])[0]
+                code = known.get(g)
+                if code is None:
+                    code = known[g] = gt_call_code(g)
+                row[s] = code
+            rows.append(bytes(row))
+    n = len(chrom)
+    codes = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(n, len(names)).copy() if n else np.zeros((0, len(names)), dtype=np.uint8)
+    return {"samples": np.array(names, dtype="U"), "has_gt": any_gt or n == 0, "chr": np.array(chrom, dtype="U"),
+            "pos": np.array(pos, dtype=int), "codes": codes}
+
+
+def _sample_count(path):
+    """sample columns named by the #CHROM line"""
+    with _open(path) as fh:
+        for line in fh:
+            if line.startswith("#CHROM"):
+                return len(line.rstrip("\n").split("\t")[9:])
+            if not line.startswith("#"):
+                break
+    return 0
+
+
 def read_calls(path, samples=(0,), native=True):
+    if samples is None:                          # every sample column (the reference's samples_to_load=None)
+        samples = tuple(range(_sample_count(path)))
     if native and len(samples) == 1:
         fast = _read_calls_native(path, int(samples[0]))
         if fast is not None:

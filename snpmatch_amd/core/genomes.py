@@ -90,6 +90,21 @@ class Genome(object):
             return lookup(echr)
         return np.array([lookup(str(e)) for e in np.asarray(echr)], dtype="int8")
 
+    def estimated_cM_distance(self, snp_position):
+        """genetic position in cM of 'chr1,150000' (or of the middle of 'chr1,1,300000'): the chromosome's mean recombination
+        rate (``recomb_rates`` of the genome JSON, cM per Mb; 3 for every chromosome when the file has none) times the
+        physical position in Mb (interface of the reference's core/genomes.py:53-70)"""
+        if "recomb_rates" in self.json.keys():
+            rates = self.json['recomb_rates']
+        else:
+            log.warning("Average recombination rates were missing in genome file. Add rates for each chromosome as an array in genome json file under 'recomb_rates' key. Using default rate of 3")
+            rates = np.repeat(3, len(self.chrs_ids))
+        assert isinstance(snp_position, str), "expected a string!"
+        parts = snp_position.split(",")
+        assert len(parts) >= 2, "input should be 'chr1,1000' or 'chr1,1000,2000'"
+        where = int(parts[1]) if len(parts) == 2 else (int(parts[1]) + int(parts[2])) / 2
+        return rates[self.get_chr_ind(str(parts[0]))] * where / 1000000
+
     def _check(self, ids, what):
         assert len(ids) <= len(self.chrs_ids), _MISMATCH
         shared = np.intersect1d(ids, self.chrs_ids)

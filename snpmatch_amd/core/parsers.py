@@ -68,6 +68,51 @@ def parseGT(snpGT, _sep=None):
     return codes
 
 
+GT_NO_SEPARATOR = 0xFF
+_GT_CLASS_VALUE = np.array([0, 1, 2, -1, 0, 0, 0, 0], dtype=np.int8)      # class (bits 0-2 of a call code) -> parseGT's value
+
+
+def gt_call_code(text):
+    """Call code of ONE genotype text, the unit ``genotype_cross`` sends to the device: bits 0-2 the class -- 0 ``0s0``, 1 ``1s1``,
+    2 ``0s1`` / ``1s0``, 3 ``.s.``, 4 any other text holding a separator -- bit 3 set when the separator ``s`` is ``|`` (which wins
+    over ``/`` when both occur, as in ``parseGT``); ``GT_NO_SEPARATOR`` (0xFF) for a text without one (haploid calls).
+    ``gt_call_code`` of the library's VCF reader is the C++ twin."""
+    text = str(text)
+    sep = _gt_separator(text)
+    if sep is None:
+        return GT_NO_SEPARATOR
+    hi = 8 if sep == "|" else 0
+    if len(text) == 3 and text[1] == sep:
+        pair = text[0] + text[2]
+        if pair == "00":
+            return hi
+        if pair == "11":
+            return hi | 1
+        if pair in ("01", "10"):
+            return hi | 2
+        if pair == "..":
+            return hi | 3
+    return hi | 4
+
+
+def gt_call_codes(gt):
+    """``gt_call_code`` of every entry of a text array (any shape) -> uint8 of that shape; the distinct texts are coded once"""
+    gt = np.asarray(gt)
+    if gt.size == 0:
+        return np.zeros(gt.shape, dtype=np.uint8)
+    uniq, inverse = np.unique(gt.astype("U"), return_inverse=True)
+    table = np.array([gt_call_code(u) for u in uniq.tolist()], dtype=np.uint8)
+    return table[np.asarray(inverse).reshape(gt.shape)]
+
+
+def call_code_values(codes, governing_bar):
+    """what ``parseGT`` makes of coded calls when the FIRST text it is given uses '|' (``governing_bar`` True) or '/': the class
+    value under that separator, 0 for a call written with the other one.  int8, shape of ``codes``."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    mine = ((codes >> 3) & 1).astype(bool) == np.asarray(governing_bar, dtype=bool)
+    return np.where(mine, _GT_CLASS_VALUE[codes & 7], 0).astype(np.int8)
+
+
 def snp_binary_to_gt(snpBinary):
     codes = np.array(snpBinary, dtype="int8")
     out = np.zeros(len(codes), dtype="S8")
@@ -370,8 +415,8 @@ class ParseInputs(object):
 def import_vcf_file(inFile, logDebug=False, samples_to_load=[0], add_fields=None):
     """dict with 'samples', 'gt' [n, s], 'wei' (the PL triples, -1 = missing; only when PL occurs), 'chr',
     'pos', 'dp' (INFO/DP, or "NA" entries when the file has none) -- the keys the reference builds from
-    scikit-allel's output"""
-    calls = _vcf.read_calls(inFile, tuple(samples_to_load))
+    scikit-allel's output.  ``samples_to_load`` None: every sample column, as in the reference."""
+    calls = _vcf.read_calls(inFile, None if samples_to_load is None else tuple(samples_to_load))
     if not calls["has_gt"]:
         die("input VCF file doesnt have required GT field")
     out = {'samples': calls["samples"], 'gt': calls["gt"], 'chr': calls["chr"], 'pos': calls["pos"], 'called': calls.get("called")}
@@ -381,6 +426,16 @@ def import_vcf_file(inFile, logDebug=False, samples_to_load=[0], add_fields=None
     for name in (add_fields or ()):
         log.warning("Field %s is not loaded by this reader" % name)
     return out
+
+
+def import_vcf_calls(inFile, logDebug=False, native=True):
+    """Every sample column of a VCF as call codes (``gt_call_code``), without the genotype text matrix: dict with 'samples',
+    'chr', 'pos' and 'codes' uint8 [n_records, n_samples].  The library's single-pass reader serves it; the Python reader takes
+    the files it declines (``native`` False: always).  What ``genotype_cross`` reads its F2 population with."""
+    calls = _vcf.read_call_codes(inFile, native=native)
+    if not calls["has_gt"]:
+        die("input VCF file doesnt have required GT field")
+    return {'samples': calls["samples"], 'chr': calls["chr"], 'pos': calls["pos"], 'codes': calls["codes"]}
 
 
 def potatoParser(inFile, logDebug, outFile="parser"):

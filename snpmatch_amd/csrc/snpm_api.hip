@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross"};
 
 struct Buf {
     void *p = nullptr;
@@ -66,6 +66,7 @@ struct snpm_ctx {
     Buf ws_lik_y, ws_lik_n, ws_lik_l, ws_lik_r;
     Buf ws_wprops, ws_epart;            // partial sums of k_wprops / k_eref
     int once_tail = 1;                  // SNPM_ONCE_TAIL=0: snpm_genotype_once ends with k_scan_few + k_once_finish instead of k_once_tail
+    Buf ws_gc_codes, ws_gc_par, ws_gc_off, ws_gc_geno, ws_gc_counts;   // snpm_cross_calls (snpm_api_gcross.hpp)
     Buf ws_once, ws_once_table;         // packed results of snpm_genotype_once; the weight table of its coded form
     std::vector<double> once_table;     // host image of ws_once_table
     std::vector<uint8_t> once_code_flags;   // per code: bit 0 a fractional / huge entry, 1 neither 0 nor 1, 2 NaN / infinite, 3 past the table
@@ -546,7 +547,8 @@ int snpm_destroy(snpm_ctx *ctx)
                        &ctx->ws_seg_desc, &ctx->ws_eseg, &ctx->ws_pairs, &ctx->ws_pair_sums, &ctx->ws_bscore, &ctx->ws_bninfo, &ctx->ws_bout,
                        &ctx->ws_blut, &ctx->ws_brows, &ctx->ws_brows32, &ctx->ws_bw, &ctx->ws_bcodes,
                        &ctx->ws_sh_bitmap, &ctx->ws_sh_wordbase, &ctx->ws_sh_blocks, &ctx->ws_sh_urows, &ctx->ws_sh_meta, &ctx->ws_sh_A,
-                       &ctx->ws_sh_pos, &ctx->ws_sh_partial};
+                       &ctx->ws_sh_pos, &ctx->ws_sh_partial,
+                       &ctx->ws_gc_codes, &ctx->ws_gc_par, &ctx->ws_gc_off, &ctx->ws_gc_geno, &ctx->ws_gc_counts};
         for (Buf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -608,6 +610,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_carry.hpp"
 
 #include "snpm_api_oneshot.hpp"
+
+#include "snpm_api_gcross.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

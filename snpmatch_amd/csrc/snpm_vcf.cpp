@@ -37,6 +37,11 @@ struct VcfChunk {
     std::vector<double> pl;                   // n * 3
     size_t chr_width = 1, gt_width = 1;
     bool any_gt = false, any_pl = false, any_dp = false, ok = true, ascii = true;
+    // every sample column as one call code per record (snpm_vcf_parse_calls): n * ncol bytes; ncol = sample columns of the block's
+    // records (-1: none seen yet), uniform = every record of the block has that many
+    std::vector<uint8_t> codes;
+    long ncol = -1;
+    bool uniform = true;
 };
 
 struct snpm_vcf {
@@ -46,6 +51,7 @@ struct snpm_vcf {
     size_t n = 0;
     size_t chr_width = 1, gt_width = 1;
     bool any_gt = false, any_pl = false, any_dp = false, ascii = true;
+    bool calls = false;                       // parsed by snpm_vcf_parse_calls: the chunks hold call codes of every sample, no GT text / PL
 };
 
 namespace {
@@ -107,13 +113,33 @@ inline bool parse_double(const char *p, size_t n, double *v)
     return true;
 }
 
-// every line of [s, end) into the chunk
+// Call code of one genotype text (include/snpmatch_hip.h, snpm_cross_calls): bits 0-2 the class -- 0 '0s0', 1 '1s1', 2 '0s1' / '1s0',
+// 3 '.s.', 4 any other text that holds a separator -- and bit 3 set when the separator s is '|' ('|' wins when both occur: parseGT
+// looks for it first, core/parsers.py:17-22); 0xFF for a text without a separator.  parsers.gt_call_codes is the Python twin.
+inline uint8_t gt_call_code(const char *p, size_t n)
+{
+    const bool bar = memchr(p, '|', n) != nullptr;
+    if (!bar && memchr(p, '/', n) == nullptr) return 0xFF;
+    const char sep = bar ? '|' : '/';
+    const uint8_t hi = bar ? 8 : 0;
+    if (n == 3 && p[1] == sep) {
+        const char a = p[0], b = p[2];
+        if (a == '0' && b == '0') return hi | 0;
+        if (a == '1' && b == '1') return hi | 1;
+        if ((a == '0' && b == '1') || (a == '1' && b == '0')) return hi | 2;
+        if (a == '.' && b == '.') return hi | 3;
+    }
+    return hi | 4;
+}
+
+// every line of [s, end) into the chunk; sample_index -1: every sample column, as call codes
 static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_index)
 {
     constexpr int MAXF = 4096;
     std::vector<Field> f(MAXF);
     Field keys[64], vals[64], nums[4];
     bool ok = true;
+    const bool all = sample_index < 0;
     while (s < end && ok) {
         const char *nl = (const char *)memchr(s, '\n', (size_t)(end - s));
         const char *e = nl ? nl : end;
@@ -132,9 +158,10 @@ static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_
             continue;
         }
         const int want = 10 + sample_index;
-        const int nf = split(s, e, '\t', f.data(), want + 1);
+        const int nf = split(s, e, '\t', f.data(), all ? MAXF : want + 1);
         s = next;
         if (nf < 8) continue;
+        if (all && nf == MAXF) { ok = false; break; }
         int64_t pos;
         if (!parse_int(f[1].p, f[1].n, &pos)) { ok = false; break; }
         // INFO/DP: first item starting with "DP="
@@ -164,7 +191,23 @@ static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_
             if (nk == 64) { ok = false; break; }
             for (int k = 0; k < nk; ++k)
                 if (keys[k].n == 2 && keys[k].p[0] == 'G' && keys[k].p[1] == 'T') v->any_gt = true;
-            if (nf > 9 + sample_index) {
+            if (all) {
+                // the GT entry of every sample column ('./.' where the column has none, a bare '.' is './.': _vcf._sample_fields)
+                const long ncol = nf - 9;
+                if (v->ncol < 0) v->ncol = ncol;
+                v->uniform &= (ncol == v->ncol);
+                for (int c = 9; c < nf; ++c) {
+                    const int nv = split(f[c].p, f[c].p + f[c].n, ':', vals, 64);
+                    if (nv == 64) { ok = false; break; }
+                    const int m = nk < nv ? nk : nv;
+                    uint8_t code = 3;
+                    for (int k = 0; k < m; ++k)
+                        if (keys[k].n == 2 && keys[k].p[0] == 'G' && keys[k].p[1] == 'T')
+                            code = (vals[k].n == 1 && vals[k].p[0] == '.') ? 3 : gt_call_code(vals[k].p, vals[k].n);
+                    v->codes.push_back(code);
+                }
+                if (!ok) break;
+            } else if (nf > 9 + sample_index) {
                 const Field &col = f[9 + sample_index];       // exact: only field `want` can hold the rest of the line
                 const int nv = split(col.p, col.p + col.n, ':', vals, 64);
                 if (nv == 64) { ok = false; break; }
@@ -187,6 +230,10 @@ static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_
                 if (!ok) break;
             }
         }
+        if (all && nf <= 8) {                 // a record without FORMAT / sample columns
+            if (v->ncol < 0) v->ncol = 0;
+            v->uniform &= (v->ncol == 0);
+        }
         if (gt_n > 64 || f[0].n > 256 || v->chr_text.size() + f[0].n >= 0xFFFFFF00u || v->gt_text.size() + gt_n >= 0xFFFFFF00u) {
             ok = false;
             break;
@@ -196,11 +243,12 @@ static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_
         v->any_pl |= has_pl;
         v->chr_text.append(f[0].p, f[0].n);
         v->chr_off.push_back((uint32_t)v->chr_text.size());
+        v->pos.push_back(pos);
+        if (f[0].n > v->chr_width) v->chr_width = f[0].n;
+        if (all) continue;                    // call codes only: no GT text, PL or depth is kept
         v->gt_text.append(gt_p, gt_n);
         v->gt_off.push_back((uint32_t)v->gt_text.size());
-        if (f[0].n > v->chr_width) v->chr_width = f[0].n;
         if (gt_n > v->gt_width) v->gt_width = gt_n;
-        v->pos.push_back(pos);
         v->dp.push_back(dp);
         v->pl.push_back(pl[0]);
         v->pl.push_back(pl[1]);
@@ -270,9 +318,11 @@ extern "C" {
 // small team of threads and kept in file order (round 3 parsed on the reading thread: 0.7 s of a 1M-record file).
 // No C++ exception leaves this function (ctypes would turn it into std::terminate): running out of host memory
 // on a very large file is reported as SNPM_ERR_STATE, i.e. "use the generic reader", like any other declined file.
-int snpm_vcf_parse(const char *path, int sample_index, snpm_vcf **out)
+static void for_each_chunk(const snpm_vcf *v, const std::function<void(const VcfChunk &, size_t)> &fn);
+
+static int vcf_parse_impl(const char *path, int sample_index, snpm_vcf **out)
 try {
-    if (!path || !out || sample_index < 0 || sample_index > 4000) return SNPM_ERR_BADARG;
+    if (!path || !out || sample_index < -1 || sample_index > 4000) return SNPM_ERR_BADARG;
     std::unique_ptr<snpm_vcf> v(new snpm_vcf());
     gzFile gz = gzopen(path, "rb");          // transparently reads plain text as well
     if (!gz) return SNPM_ERR_BADARG;
@@ -477,7 +527,47 @@ try {
         if (ch->has_names) v->sample_names = ch->sample_names;      // the last #CHROM line of the file, as before
     }
     v->n = v->first.back();
+    if (sample_index < 0) {
+        // every record must carry exactly the sample columns the header names: anything else is the generic reader's to interpret
+        v->calls = true;
+        for (const auto &ch : v->chunks)
+            if (!ch->pos.empty() && (!ch->uniform || ch->ncol != (long)v->sample_names.size())) return SNPM_ERR_STATE;
+    }
     *out = v.release();
+    return SNPM_OK;
+} catch (...) {
+    return SNPM_ERR_STATE;
+}
+
+int snpm_vcf_parse(const char *path, int sample_index, snpm_vcf **out)
+{
+    if (sample_index < 0) return SNPM_ERR_BADARG;
+    return vcf_parse_impl(path, sample_index, out);
+}
+
+int snpm_vcf_parse_calls(const char *path, snpm_vcf **out) { return vcf_parse_impl(path, -1, out); }
+
+// chr [n * chr_width] as UTF-32 (as snpm_vcf_fill_u32), pos [n], codes [n, ld] with the samples of a record contiguous
+int snpm_vcf_fill_calls(const snpm_vcf *v, uint32_t *chr, int64_t *pos, uint8_t *codes, int64_t ld)
+try {
+    if (!v || !v->calls) return SNPM_ERR_BADARG;
+    if (!v->ascii) return SNPM_ERR_STATE;
+    const size_t cw = v->chr_width, ns = v->sample_names.size();
+    if (codes && ld < (int64_t)ns) return SNPM_ERR_BADARG;
+    for_each_chunk(v, [&](const VcfChunk &c, size_t r0) {
+        const size_t n = c.pos.size();
+        if (chr) {
+            memset(chr + r0 * cw, 0, n * cw * sizeof(uint32_t));
+            for (size_t i = 0; i < n; ++i) {
+                const unsigned char *src = (const unsigned char *)c.chr_text.data() + c.chr_off[i];
+                const size_t len = c.chr_off[i + 1] - c.chr_off[i];
+                for (size_t k = 0; k < len; ++k) chr[(r0 + i) * cw + k] = src[k];
+            }
+        }
+        if (pos && n) memcpy(pos + r0, c.pos.data(), n * sizeof(int64_t));
+        if (codes && ns)
+            for (size_t i = 0; i < n; ++i) memcpy(codes + (r0 + i) * (size_t)ld, c.codes.data() + i * ns, ns);
+    });
     return SNPM_OK;
 } catch (...) {
     return SNPM_ERR_STATE;
@@ -514,7 +604,7 @@ static void for_each_chunk(const snpm_vcf *v, const std::function<void(const Vcf
 
 int snpm_vcf_fill(const snpm_vcf *v, char *chr, int64_t *pos, char *gt, double *pl, int64_t *dp)
 try {
-    if (!v) return SNPM_ERR_BADARG;
+    if (!v || v->calls) return SNPM_ERR_BADARG;
     const size_t cw = v->chr_width, gw = v->gt_width;
     for_each_chunk(v, [&](const VcfChunk &c, size_t r0) {
         const size_t n = c.pos.size();
@@ -541,7 +631,7 @@ try {
 // snpm_vcf_dims); SNPM_ERR_STATE otherwise (the caller converts the byte strings itself).
 int snpm_vcf_fill_u32(const snpm_vcf *v, uint32_t *chr, int64_t *pos, uint32_t *gt, double *pl, int64_t *dp, uint8_t *called)
 try {
-    if (!v) return SNPM_ERR_BADARG;
+    if (!v || v->calls) return SNPM_ERR_BADARG;
     if (!v->ascii) return SNPM_ERR_STATE;
     const size_t cw = v->chr_width, gw = v->gt_width;
     for_each_chunk(v, [&](const VcfChunk &c, size_t r0) {

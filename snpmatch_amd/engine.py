@@ -637,6 +637,34 @@ class Query(object):
             pass
 
 
+def cross_calls(ctx, codes, p1, p2, win_off, lr_thres, n_marker_thres=5, return_counts=False):
+    """genotype_cross in one device call (``snpm_cross_calls``): ``codes`` uint8 [n, n_samples] call codes of the F2 samples at
+    the matched segregating markers (rows in window order; a row-strided view such as ``m[:, :k]`` is passed as it is), ``p1`` /
+    ``p2`` the parents' calls (0 / 1 / 2, different), ``win_off`` [n_win + 1] the markers of every window.  Returns ``geno`` int8
+    [n_win, n_samples] (-1 NA, 0 parent 1, 1 heterozygous, 2 parent 2) and, with ``return_counts``, also int32 [n_win, n_samples,
+    3] = (m1, mh, m2).  ``ctx`` None: the library only validates (a sound call then fails for want of a context)."""
+    codes = np.asarray(codes)
+    assert codes.ndim == 2 and codes.dtype == np.uint8, "codes: uint8 [n, n_samples]"
+    n, ns = codes.shape
+    if n > 1 and ns > 0 and codes.strides[1] == 1 and codes.strides[0] >= ns:
+        ld = codes.strides[0]               # rows with padding behind them travel as they are
+    else:
+        codes, ld = np.ascontiguousarray(codes), ns
+    p1 = np.ascontiguousarray(p1, dtype=np.int8)
+    p2 = np.ascontiguousarray(p2, dtype=np.int8)
+    assert len(p1) == n and len(p2) == n, "one parental call per marker"
+    win_off = np.ascontiguousarray(win_off, dtype=np.int64)
+    n_win = len(win_off) - 1
+    assert n_win >= 0, "win_off holds n_win + 1 entries"
+    geno = np.empty((n_win, ns), dtype=np.int8)
+    counts = np.empty((n_win, ns, 3), dtype=np.int32) if return_counts else None
+    lib = ctx.lib if ctx is not None else _lib.load()
+    h = ctx.h if ctx is not None else None
+    check(lib.snpm_cross_calls(h, ptr(codes), n, ns, ld, ptr(p1), ptr(p2), ptr(win_off), n_win, float(lr_thres), int(n_marker_thres),
+                               ptr(geno), ptr(counts)), h)
+    return (geno, counts) if return_counts else geno
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the

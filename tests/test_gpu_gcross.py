@@ -1,0 +1,180 @@
+"""genotype_cross on the device: ``snpm_cross_calls`` / ``k_gcross`` against the reference's goldens and the numpy twin
+(tests/gcross_twin.py), whole files through ``GenotypeCross`` and the command line on int8 and packed panels, and random codes at
+the shapes where the kernel's decomposition (4 samples per lane, 256 per tile, rows split over 4 waves) could break."""
+import numpy as np
+import pytest
+
+import gcross_twin
+import gcross_util
+from snpmatch_amd import cli, engine
+from snpmatch_amd.core import genomes, genotype_cross, snp_genotype
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return engine.default_context()
+
+
+def _device_step(ctx, record):
+    def step(codes, p1, p2, win_off, lr_thres):
+        geno, counts = engine.cross_calls(ctx, codes, p1, p2, win_off, lr_thres, return_counts=True)
+        record.update(geno=geno, counts=counts, args=(codes, p1, p2, win_off, lr_thres))
+        return geno
+    return step
+
+
+@pytest.mark.parametrize("name", gcross_util.CASES)
+def test_goldens_through_the_device_call(name, ctx, tmp_path, monkeypatch):
+    case = gcross_util.load(name)
+    seen = {}
+    monkeypatch.setattr(genotype_cross, "genome", genomes.Genome(gcross_util.write_genome(case, str(tmp_path / "genome.json"))))
+    monkeypatch.setattr(genotype_cross, "count_and_decide", _device_step(ctx, seen))
+    vcf = gcross_util.write_vcf(str(tmp_path / "f2.vcf"), case["vcf_chr"], case["vcf_pos"], case["vcf_gt"], case["samples"])
+    cross = genotype_cross.GenotypeCross(gcross_util.DuckGenotype(case), str(case["parents"]), int(case["binLen"]), None, False)
+    lines = cross.genotype_cross(vcf, float(case["lr_thres"]))
+    t_geno, t_counts, lr_next = gcross_twin.cross_calls(*seen["args"])
+    assert gcross_twin.knife_edge_cells(lr_next, float(case["lr_thres"])) == 0
+    assert np.array_equal(seen["counts"], case["counts"]) and np.array_equal(seen["counts"], t_counts)
+    assert np.array_equal(seen["geno"], case["geno"]) and np.array_equal(seen["geno"], t_geno)
+    assert lines.tolist() == case["lines"].tolist()
+
+
+def _db_file(case, path):
+    np.savez(path, snps=case["panel"], accessions=case["accessions"].astype("S"), positions=case["positions"],
+             chrs=case["chrs"].astype("S"), chr_regions=case["chr_regions"])
+    return path
+
+
+@pytest.mark.parametrize("packed", [False, True], ids=["int8", "packed"])
+@pytest.mark.parametrize("name", ["gcross_a_f2", "gcross_b_phasing", "gcross_d_sparse"])
+def test_whole_file_on_a_resident_panel(name, packed, ctx, tmp_path, monkeypatch):
+    case = gcross_util.load(name)
+    monkeypatch.setattr(genotype_cross, "genome", genomes.Genome(gcross_util.write_genome(case, str(tmp_path / "genome.json"))))
+    g = snp_genotype.Genotype.from_arrays(case["panel"], case["accessions"], case["positions"], case["chrs"], case["chr_regions"])
+    panel = g.panel(ctx, packed=packed)
+    assert bool(panel.packed) == packed
+    vcf = gcross_util.write_vcf(str(tmp_path / "f2.vcf.gz"), case["vcf_chr"], case["vcf_pos"], case["vcf_gt"], case["samples"])
+    cross = genotype_cross.GenotypeCross(g, str(case["parents"]), int(case["binLen"]), None, False)
+    out = str(tmp_path / "out.csv")
+    cross.write_output_genotype_cross(cross.genotype_cross(vcf, float(case["lr_thres"])), out)
+    panel.free()
+    assert open(out).read() == "".join(ln + "\n" for ln in case["lines"].tolist())
+
+
+@pytest.mark.parametrize("packed", ["0", "1"], ids=["int8", "packed"])
+@pytest.mark.parametrize("name", ["gcross_c_multiallelic", "gcross_f_thres2706"])
+def test_command_line_writes_the_reference_file(name, packed, tmp_path, monkeypatch):
+    case = gcross_util.load(name)
+    monkeypatch.setenv("SNPMATCH_PACKED", packed)
+    db = _db_file(case, str(tmp_path / "db.npz"))
+    vcf = gcross_util.write_vcf(str(tmp_path / "f2.vcf"), case["vcf_chr"], case["vcf_pos"], case["vcf_gt"], case["samples"])
+    out = str(tmp_path / "out.csv")
+    rc = cli.main(["genotype_cross", "-i", vcf, "-d", db, "-p", str(case["parents"]), "-b", str(int(case["binLen"])),
+                   "--genome", gcross_util.write_genome(case, str(tmp_path / "genome.json")), "--lr_thres", str(float(case["lr_thres"])),
+                   "-o", out])
+    assert rc == 0
+    assert open(out).read() == "".join(ln + "\n" for ln in case["lines"].tolist())
+
+
+def test_parent_with_codes_above_two_is_read_on_the_host_and_refused(ctx, tmp_path, monkeypatch):
+    case = gcross_util.load("gcross_d_sparse")
+    snps = case["panel"].copy()
+    monkeypatch.setattr(genotype_cross, "genome", genomes.Genome(gcross_util.write_genome(case, str(tmp_path / "genome.json"))))
+    vcf = gcross_util.write_vcf(str(tmp_path / "f2.vcf"), case["vcf_chr"], case["vcf_pos"], case["vcf_gt"], case["samples"])
+    g = snp_genotype.Genotype.from_arrays(snps, case["accessions"], case["positions"], case["chrs"], case["chr_regions"])
+    g.panel(ctx, packed=False)
+    cross = genotype_cross.GenotypeCross(g, str(case["parents"]), int(case["binLen"]), None, False)
+    rows = g.get_positions_idxs(case["vcf_chr"], case["vcf_pos"])[0]
+    snps[rows[5], cross.p1_ix] = 3                            # (the resident panel holds the earlier value: the host read must win)
+    g.panel().free()
+    g._panel = None
+    g.panel(ctx, packed=False)
+    one, two = cross._parent_calls(rows)
+    assert np.array_equal(one, snps[rows, cross.p1_ix]) and np.array_equal(two, snps[rows, cross.p2_ix]) and one[5] == 3
+    if snps[rows[5], cross.p2_ix] >= 0:
+        with pytest.raises(ValueError, match="call codes other than"):
+            cross.genotype_cross(vcf, 1.5)
+    g.panel().free()
+
+
+# ------------------------------------------------------------------------------------------------ random codes at the kernel's edges
+SIZES = [0, 0, 1, 4, 5, 0, 63, 64, 65, 700, 3, 0, 0]          # empty windows first, last and adjacent; 700 rows: 175 per wave
+LR_THRES = 1.5
+_cases = {}
+
+
+def _random_case(n_samples):
+    """(padded codes, p1, p2, win_off, twin geno, twin counts): made once per width, kept unchanged"""
+    if n_samples not in _cases:
+        rng = np.random.default_rng(1000 + n_samples)
+        win_off = np.concatenate(([0], np.cumsum(SIZES))).astype(np.int64)
+        n, n_win = int(win_off[-1]), len(SIZES)
+        p1 = rng.integers(0, 3, size=n).astype(np.int8)
+        p2 = ((p1 + rng.integers(1, 3, size=n)) % 3).astype(np.int8)
+        window = np.repeat(np.arange(n_win), SIZES)
+        state = rng.integers(0, 4, size=(n_win, n_samples))[window]               # parent 1, het, parent 2, anything
+        value = np.where(state == 0, p1[:, None], np.where(state == 1, 2, np.where(state == 2, p2[:, None], rng.integers(0, 3, size=(n, n_samples)))))
+        noise = rng.random((n, n_samples))
+        cls = np.where(noise < 0.10, rng.integers(0, 3, size=(n, n_samples)), value)
+        cls = np.where(noise > 0.97, 4, np.where(noise > 0.92, 3, cls))
+        # separators: odd samples are phased, 10 % of all calls use the other one -- also in the first row of a window, so the
+        # governing separator differs between the samples of one window
+        bar = (np.arange(n_samples)[None, :] % 2 == 1) ^ (rng.random((n, n_samples)) < 0.10)
+        codes = (cls | (bar.astype(np.int64) << 3)).astype(np.uint8)
+        first = codes[win_off[:-1][np.array(SIZES) > 0]] >> 3
+        assert n_samples < 3 or np.any(first.min(axis=1) != first.max(axis=1))
+        padded = np.full((n, n_samples + 7), 0xEE, dtype=np.uint8)
+        padded[:, :n_samples] = codes
+        geno, counts, lr_next = gcross_twin.cross_calls(codes, p1, p2, win_off, LR_THRES)
+        assert gcross_twin.knife_edge_cells(lr_next, LR_THRES) == 0                # the seeds are fixed so that this holds
+        for a in (padded, p1, p2, win_off, geno, counts):
+            a.flags.writeable = False
+        _cases[n_samples] = (padded, p1, p2, win_off, geno, counts)
+    return _cases[n_samples]
+
+
+@pytest.mark.parametrize("n_samples", [1, 3, 64, 65, 257])
+def test_random_codes_against_the_twin(n_samples, ctx):
+    padded, p1, p2, win_off, want_geno, want_counts = _random_case(n_samples)
+    view = padded[:, :n_samples]                              # ld = n_samples + 7, the columns behind hold 0xEE
+    geno, counts = engine.cross_calls(ctx, view, p1, p2, win_off, LR_THRES, return_counts=True)
+    assert np.array_equal(counts, want_counts)
+    assert np.array_equal(geno, want_geno)
+    assert len(np.unique(want_geno)) == (4 if n_samples > 1 else len(np.unique(want_geno)))     # NA, 0, 1 and 2 all occur
+    assert np.array_equal(engine.cross_calls(ctx, view, p1, p2, win_off, LR_THRES), want_geno)  # counts == NULL: the same calls
+    # other thresholds move calls between 0 / 2 and NA only, and only as the twin says
+    for thres in (1.0, 2.706):
+        t_geno, _, lr_next = gcross_twin.cross_calls(padded[:, :n_samples], p1, p2, win_off, thres)
+        assert gcross_twin.knife_edge_cells(lr_next, thres) == 0
+        assert np.array_equal(engine.cross_calls(ctx, view, p1, p2, win_off, thres), t_geno)
+    # a marker threshold other than 5
+    t_geno, _, _ = gcross_twin.cross_calls(padded[:, :n_samples], p1, p2, win_off, LR_THRES, n_marker_thres=64)
+    assert np.array_equal(engine.cross_calls(ctx, view, p1, p2, win_off, LR_THRES, n_marker_thres=64), t_geno)
+
+
+def test_no_markers_and_no_windows(ctx):
+    geno, counts = engine.cross_calls(ctx, np.zeros((0, 5), dtype=np.uint8), [], [], [0, 0, 0, 0], 1.5, return_counts=True)
+    assert geno.shape == (3, 5) and np.all(geno == -1) and not counts.any()
+    assert engine.cross_calls(ctx, np.zeros((0, 5), dtype=np.uint8), [], [], [0], 1.5).shape == (0, 5)
+    assert engine.cross_calls(ctx, np.zeros((4, 0), dtype=np.uint8), [0, 0, 1, 2], [1, 2, 0, 0], [0, 4], 1.5).shape == (1, 0)
+    with pytest.raises(AssertionError, match="end at n"):
+        engine.cross_calls(ctx, np.zeros((4, 2), dtype=np.uint8), [0, 0, 1, 2], [1, 2, 0, 0], [0, 3], 1.5)
+
+
+def test_one_window_per_separator_rule(ctx):
+    """a hand-made window: the first row governs, calls written with the other separator read as 0 (hom-ref), also '1|1'"""
+    from snpmatch_amd.core import parsers
+    col_a = ["0/0", "1|1", "1/1", "0|1", "1/1", "./.", "1/2", "1/1"]      # governed by '/': values 0 0 1 0 1 -1 0 1
+    col_b = ["1|1", "1/1", "1|1", "0|1", "1|0", ".|.", "./.", "0|0"]      # governed by '|': values 1 0 1 2 2 -1 0 0
+    codes = parsers.gt_call_codes(np.array([col_a, col_b]).T)
+    p1 = np.array([1, 1, 1, 1, 1, 1, 1, 1], dtype=np.int8)
+    p2 = np.array([0, 0, 0, 0, 0, 0, 0, 0], dtype=np.int8)
+    geno, counts = engine.cross_calls(ctx, codes, p1, p2, [0, 8], 1.5, return_counts=True)
+    assert counts[0].tolist() == [[3, 0, 4], [2, 2, 3]]
+    t_geno, t_counts, _ = gcross_twin.cross_calls(codes, p1, p2, [0, 8], 1.5)
+    assert np.array_equal(counts, t_counts) and np.array_equal(geno, t_geno)
+    for s, col in enumerate((col_a, col_b)):
+        want = genotype_cross.GenotypeCross.get_window_genotype_gts(np.array(col), p1, p2, 1.5)[0]
+        assert (-1 if want == 'NA' else want) == geno[0, s]
