@@ -44,6 +44,22 @@ struct Buf {
 
 }  // namespace
 
+// The grow-only device workspaces of a context (ensure()).  This ONE list declares the members of snpm_ctx and is what
+// snpm_destroy walks: a workspace cannot be declared without being freed.
+#define SNPM_CTX_WORKSPACES(X)                                                                                                    \
+    X(ws_grp_score) X(ws_grp_miss) X(ws_stage_dev) X(ws_flags2)                                                                   \
+    X(ws_part_score) X(ws_part_miss) X(ws_seg_score) X(ws_seg_miss) X(ws_seg_off) X(ws_cols) X(ws_tmp_score) X(ws_tmp_ninfo)      \
+    X(ws_flags) X(ws_lik_y) X(ws_lik_n) X(ws_lik_l) X(ws_lik_r)                                                                   \
+    X(ws_wprops) X(ws_epart)                        /* partial sums of k_wprops / k_eref */                                       \
+    X(ws_gc_codes) X(ws_gc_par) X(ws_gc_off) X(ws_gc_geno) X(ws_gc_counts)      /* snpm_cross_calls (snpm_api_gcross.hpp) */      \
+    X(ws_once) X(ws_once_table)     /* snpm_genotype_once: its packed results (unfused form); the weight table of its coded form */ \
+    X(ws_once_state)                /* {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls */             \
+    /* segmented / batched scoring */                                                                                             \
+    X(ws_seg_desc) X(ws_eseg) X(ws_pairs) X(ws_pair_sums) X(ws_bscore) X(ws_bninfo) X(ws_bout) X(ws_blut) X(ws_brows)             \
+    X(ws_brows32) X(ws_bw) X(ws_bcodes)                                                                                           \
+    /* shared-row scan of a batch (snpm_api_shared.hpp): union of the samples' rows, the int8 digit matrix, partial digit sums */ \
+    X(ws_sh_bitmap) X(ws_sh_wordbase) X(ws_sh_blocks) X(ws_sh_urows) X(ws_sh_meta) X(ws_sh_A) X(ws_sh_pos) X(ws_sh_partial)
+
 struct snpm_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -60,23 +76,16 @@ struct snpm_ctx {
     // pinned host buffer for small result readbacks (exactness check)
     void *h_pinned = nullptr;
     size_t h_pinned_cap = 0;
-    // grow-only device workspaces
-    Buf ws_grp_score, ws_grp_miss, ws_stage_dev, ws_flags2;
-    Buf ws_part_score, ws_part_miss, ws_seg_score, ws_seg_miss, ws_seg_off, ws_cols, ws_tmp_score, ws_tmp_ninfo, ws_flags;
-    Buf ws_lik_y, ws_lik_n, ws_lik_l, ws_lik_r;
-    Buf ws_wprops, ws_epart;            // partial sums of k_wprops / k_eref
+    // grow-only device workspaces: SNPM_CTX_WORKSPACES (above) declares them, snpm_destroy frees what it lists
+#define X(name) Buf name;
+    SNPM_CTX_WORKSPACES(X)
+#undef X
     int once_tail = 1;                  // SNPM_ONCE_TAIL=0: snpm_genotype_once ends with k_scan_few + k_once_finish instead of k_once_tail
-    Buf ws_gc_codes, ws_gc_par, ws_gc_off, ws_gc_geno, ws_gc_counts;   // snpm_cross_calls (snpm_api_gcross.hpp)
-    Buf ws_once, ws_once_table;         // packed results of snpm_genotype_once; the weight table of its coded form
     std::vector<double> once_table;     // host image of ws_once_table
     std::vector<uint8_t> once_code_flags;   // per code: bit 0 a fractional / huge entry, 1 neither 0 nor 1, 2 NaN / infinite, 3 past the table
     std::vector<double> once_code_abs;  // per code: |entry| (0 for codes past the table and non-finite entries)
-    Buf ws_once_state;                  // {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls
     bool once_state_clean = false;
     int once_fused = 1;                 // SNPM_ONCE_FUSED=0: snpm_genotype_once keeps the unfused kernels and copies of its first version
-    Buf ws_seg_desc, ws_eseg, ws_pairs, ws_pair_sums, ws_bscore, ws_bninfo, ws_bout, ws_blut, ws_brows, ws_brows32, ws_bw, ws_bcodes;   // segmented / batched scoring
-    // shared-row scan of a batch (snpm_api_shared.hpp): union of the samples' rows, the int8 digit matrix, partial digit sums
-    Buf ws_sh_bitmap, ws_sh_wordbase, ws_sh_blocks, ws_sh_urows, ws_sh_meta, ws_sh_A, ws_sh_pos, ws_sh_partial;
     int batch_shared = -1;              // SNPM_BATCH_SHARED / snpm_batch_configure: -1 auto (batches whose inputs are on the device), 0 never, 1 whenever the batch allows it
     int shared_digits = 0;              // base-256 digits of the fixed-point weights (3..7: 2^-(8 (digits - 1) + 6) per matched SNP of quantisation); 0 = by the longest sample
     int shared_min_samples = 4;         // auto: smaller batches keep the per-sample pass (2 / 3 / 4 / 6 samples of 194k SNPs on one marker set: 0.28 / 0.29 / 0.30 / 0.32 ms
@@ -541,16 +550,9 @@ int snpm_destroy(snpm_ctx *ctx)
     ctx->carries.clear();
     if (use_hip) {
         for (auto &c : ctx->qcache) (void)hipFree(c.p);
-        Buf *bufs[] = {&ctx->ws_stage_dev, &ctx->ws_flags2, &ctx->ws_grp_score, &ctx->ws_grp_miss, &ctx->ws_part_score, &ctx->ws_part_miss, &ctx->ws_seg_score, &ctx->ws_seg_miss, &ctx->ws_seg_off,
-                       &ctx->ws_cols, &ctx->ws_tmp_score, &ctx->ws_tmp_ninfo, &ctx->ws_flags, &ctx->ws_lik_y,
-                       &ctx->ws_lik_n, &ctx->ws_lik_l, &ctx->ws_lik_r, &ctx->ws_wprops, &ctx->ws_epart,
-                       &ctx->ws_seg_desc, &ctx->ws_eseg, &ctx->ws_pairs, &ctx->ws_pair_sums, &ctx->ws_bscore, &ctx->ws_bninfo, &ctx->ws_bout,
-                       &ctx->ws_blut, &ctx->ws_brows, &ctx->ws_brows32, &ctx->ws_bw, &ctx->ws_bcodes,
-                       &ctx->ws_sh_bitmap, &ctx->ws_sh_wordbase, &ctx->ws_sh_blocks, &ctx->ws_sh_urows, &ctx->ws_sh_meta, &ctx->ws_sh_A,
-                       &ctx->ws_sh_pos, &ctx->ws_sh_partial,
-                       &ctx->ws_gc_codes, &ctx->ws_gc_par, &ctx->ws_gc_off, &ctx->ws_gc_geno, &ctx->ws_gc_counts};
-        for (Buf *b : bufs)
-            if (b->p) (void)hipFree(b->p);
+#define X(name) if (ctx->name.p) (void)hipFree(ctx->name.p);
+        SNPM_CTX_WORKSPACES(X)
+#undef X
         if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
         if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
         if (ctx->batch_ev) (void)hipEventDestroy(ctx->batch_ev);

@@ -291,3 +291,139 @@ def test_code_properties_follow_the_table_across_both_forms(ctx):
             assert not b["all_integer_weights"]
             assert np.array_equal(b["ninfo"], want_n) and np.array_equal(b["score"].astype(int), want_s.astype(int))
         panel.free()
+
+
+# ---- the first version's body at the sizes where its slab goes up in pieces behind the fill (more than 25 fill tasks: from
+# 102 401 fp64 rows of 4096 per task, 204 801 coded rows of 8192 per task).  chunk = 5000 is above the fused form's limit, so the
+# default context takes that body; 64 accessions keep the scoring small.
+BIG_CHUNK = 5000
+
+
+def _pl_sample(rng, n_in):
+    """PL-weighted weights [n_in, 3] (one row in ten one-hot) and their dictionary codes"""
+    from snpmatch_amd.core import parsers
+    pl = rng.integers(0, 256, size=(n_in, 3)).astype(float)
+    pl[rng.random(n_in) < 0.1] = -1.0
+    no_pl = np.all(pl == -1, axis=1)
+    wei = np.exp(pl / (-10))
+    hot = np.zeros((int(no_pl.sum()), 3))
+    hot[np.arange(len(hot)), rng.integers(0, 3, len(hot))] = 1.0
+    wei[no_pl] = hot
+    codes, table = parsers._weight_codes(pl, no_pl, wei)
+    return wei, codes, table
+
+
+def _big_case(seed, n_snp, n_match, n_in, n_acc=64):
+    rng = np.random.default_rng(seed)
+    db = rand_db(rng, n_snp, n_acc)
+    rows = np.sort(rng.choice(n_snp, size=n_match, replace=False)).astype(np.int64)
+    sidx = np.sort(rng.choice(n_in, size=n_match, replace=False)).astype(np.int64)
+    wei, codes, table = _pl_sample(rng, n_in)
+    case = {"db": db, "n_snp": n_snp, "rows": rows, "sidx": sidx, "wei": wei, "codes": codes, "table": table}
+    case["want"] = {skip: c_oracle.genotyper(db, rows, wei[sidx], BIG_CHUNK, skip) for skip in (False, True)}
+    return case
+
+
+@pytest.fixture(scope="module")
+def big_fp64():
+    """110 000 matched rows: 27 fill tasks of 4096 fp64 rows, 2 pieces"""
+    return _big_case(611, 120000, 110000, 115000)
+
+
+@pytest.fixture(scope="module")
+def big_coded():
+    """210 000 matched rows: 26 fill tasks of 8192 coded rows, 2 pieces"""
+    return _big_case(612, 220000, 210000, 215000)
+
+
+@pytest.fixture(scope="module")
+def unfused_ctx():
+    c = _ctx_with(SNPM_ONCE_FUSED=0)
+    yield c
+    c.close()
+
+
+def _same_bits(a, b, what):
+    for k in ("score", "ninfo", "lik", "lrt"):
+        assert np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)), (what, k)
+
+
+def _check_two_pieces(ctx, unfused_ctx, case, packed, coded):
+    rows, sidx, table = case["rows"], case["sidx"], case["table"] if coded else None
+    w = case["codes"] if coded else case["wei"]
+    panel = engine.Panel.from_host(ctx, case["db"], packed=packed)
+    other = engine.Panel.from_host(unfused_ctx, case["db"], packed=packed)
+    for skip in (False, True):
+        want_s, want_n = case["want"][skip]
+        out = panel.genotype_once(rows, w, sidx, BIG_CHUNK, skip, engine.MODE_STRICT, table=table)
+        assert np.array_equal(bits(out["score"]), bits(want_s)) and np.array_equal(out["ninfo"], want_n), (packed, skip)
+        out = panel.genotype_once(rows, w, sidx, BIG_CHUNK, skip, engine.MODE_EXACT, table=table)
+        assert np.array_equal(out["ninfo"], want_n) and np.array_equal(out["score"].astype(int), want_s.astype(int)), (packed, skip)
+        if coded:
+            plain = panel.genotype_once(rows, case["wei"], sidx, BIG_CHUNK, skip, engine.MODE_EXACT)
+            _same_bits(out, plain, (packed, skip, "coded against fp64"))
+        a = panel.genotype_once(rows, w, sidx, 1000, skip, engine.MODE_EXACT, table=table)            # the fused form
+        b = other.genotype_once(rows, w, sidx, 1000, skip, engine.MODE_EXACT, table=table)            # the first version's body
+        _same_bits(a, b, (packed, skip, "fused against unfused"))
+    other.free()
+    panel.free()
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_two_piece_upload_fp64(ctx, unfused_ctx, big_fp64, packed):
+    _check_two_pieces(ctx, unfused_ctx, big_fp64, packed, coded=False)
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_two_piece_upload_coded(ctx, unfused_ctx, big_coded, packed):
+    _check_two_pieces(ctx, unfused_ctx, big_coded, packed, coded=True)
+
+
+def test_refusal_after_a_partial_upload(ctx, big_fp64, big_coded):
+    """a bad row / a bad code in a sample whose first piece is already on its way: an argument refusal on the host, and the next
+    call is a normal one"""
+    c = big_fp64
+    panel = engine.Panel.from_host(ctx, c["db"])
+    good = panel.genotype_once(c["rows"], c["wei"], c["sidx"], BIG_CHUNK, False, engine.MODE_EXACT)
+    bad_rows = c["rows"].copy()
+    bad_rows[105000] = c["n_snp"]
+    with pytest.raises(AssertionError, match="outside the panel"):
+        panel.genotype_once(bad_rows, c["wei"], c["sidx"], BIG_CHUNK, False, engine.MODE_EXACT)
+    _same_bits(panel.genotype_once(c["rows"], c["wei"], c["sidx"], BIG_CHUNK, False, engine.MODE_EXACT), good, "after a bad row")
+    panel.free()
+    c = big_coded
+    panel = engine.Panel.from_host(ctx, c["db"])
+    good = panel.genotype_once(c["rows"], c["codes"], c["sidx"], BIG_CHUNK, False, engine.MODE_EXACT, table=c["table"])
+    for at in (105000, 205000):                                  # in the first piece, in the second
+        bad_codes = c["codes"].copy()
+        bad_codes[c["sidx"][at], 1] = len(c["table"])
+        with pytest.raises(AssertionError, match="outside"):
+            panel.genotype_once(c["rows"], bad_codes, c["sidx"], BIG_CHUNK, False, engine.MODE_EXACT, table=c["table"])
+        again = panel.genotype_once(c["rows"], c["codes"], c["sidx"], BIG_CHUNK, False, engine.MODE_EXACT, table=c["table"])
+        _same_bits(again, good, "after a bad code at %d" % at)
+    panel.free()
+
+
+def test_gather_without_pool_threads(big_fp64):
+    """SNPM_STAGE_THREADS=1: the calling thread fills everything, then the pieces go up one after the other"""
+    c = big_fp64
+    one = _ctx_with(SNPM_STAGE_THREADS=1)
+    panel = engine.Panel.from_host(one, c["db"])
+    for skip in (False, True):
+        want_s, want_n = c["want"][skip]
+        out = panel.genotype_once(c["rows"], c["wei"], c["sidx"], BIG_CHUNK, skip, engine.MODE_STRICT)
+        assert np.array_equal(bits(out["score"]), bits(want_s)) and np.array_equal(out["ninfo"], want_n), skip
+    panel.free()
+    one.close()
+
+
+@pytest.mark.parametrize("n", [102400, 102401])
+def test_gather_piece_edges(ctx, big_fp64, n):
+    """exactly 25 fill tasks (one piece, nothing goes up behind the fill); 26 tasks, the second piece one row long"""
+    c = big_fp64
+    rows, wei = c["rows"][:n], c["wei"][c["sidx"][:n]]
+    want_s, want_n = c_oracle.genotyper(c["db"], rows, wei, BIG_CHUNK, False)
+    panel = engine.Panel.from_host(ctx, c["db"])
+    out = panel.genotype_once(rows, c["wei"], c["sidx"][:n], BIG_CHUNK, False, engine.MODE_STRICT)
+    assert np.array_equal(bits(out["score"]), bits(want_s)) and np.array_equal(out["ninfo"], want_n)
+    panel.free()
