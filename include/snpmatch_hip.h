@@ -428,7 +428,7 @@ int snpm_query_f1_pairs(snpm_query *query, const int32_t *acc_idx, int n_sel, do
 int snpm_debug_stream_read(snpm_panel *panel, int64_t *bytes_read);
 int snpm_profile_enable(snpm_ctx *ctx, int on);
 int snpm_profile_reset(snpm_ctx *ctx);
-/* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut".  Synchronises the stream. */
+/* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm".  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -448,6 +448,31 @@ int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, doub
 int snpm_cross_calls(snpm_ctx *ctx, const uint8_t *gt_codes, int64_t n, int n_samples, int64_t ld, const int8_t *p1, const int8_t *p2,
                      const int64_t *win_off, int n_win, double lr_thres, int n_marker_thres, int8_t *geno, int32_t *counts);
 
+/* ---------------------------------------------------------------- genotype_cross_hmm */
+/* GenotypeCross.genotype_cross_hmm (core/genotype_cross.py:113-181 of the reference: a Python loop over chromosomes x samples around
+   infer.viterbi, core/infer.py:17-58) as ONE device call: the 3-state path (0 AA, 1 AB, 2 BB) of every (chain, sample).  A chain
+   is the markers of one chromosome.  Host pointers in and out.
+     gt_codes [n, ld]     call codes (as snpm_vcf_parse_calls produces them), markers chain by chain, the samples contiguous
+     depth_rank [n, ld]   index of rint(depth) of every call among the n_depth distinct values the tables were built for
+     pair [n]             the ordered parental pair of every marker: 0 (0,1)  1 (0,2)  2 (1,0)  3 (1,2)  4 (2,0)  5 (2,1)
+     chain_off [n_chain+1] marker range of every chain: 0 = chain_off[0] <= ... <= chain_off[n_chain] = n
+     logT [n_chain][3][3] log of the transition matrix of every chain, [from][to]
+     logI, logE [6][n_depth][4][3]   log(initial x emission) and log(emission) per (pair, depth rank, observation, state)
+   Per (chain, sample): the governing separator is the one of the chain's FIRST marker of that sample; the observation of an
+   element is {0, 2, 1, 3, 0}[class] under that separator and 0 under the other one.  omega[first] = logI[...];
+   omega[r][j] = max over i of ((omega[r-1][i] + logT[i][j]) + logE[...][j]) with the FIRST maximum over i = 0, 1, 2 kept as
+   the backpointer; the last state is the first maximum of the last omega.  Additions and comparisons in fp64 only: the tables
+   carry every logarithm, -inf entries included.
+     state [n, n_samples]       the path
+     omega [n, n_samples, 3]    every step's omega; NULL to skip
+   Every argument is validated on the host before the context or the device is touched (SNPM_ERR_BADARG with a message; with ctx ==
+   NULL the message is in snpm_last_error(NULL)): chain_off from 0 to n without a decrease, ld >= n_samples, pair < 6, depth_rank <
+   n_depth, defined codes only, no NaN (or +inf) in a table, no negative size.  n == 0, n_chain == 0 or n_samples == 0 return
+   without a launch; an empty chain between two others reads nothing. */
+int snpm_cross_hmm(snpm_ctx *ctx, const uint8_t *gt_codes, const uint16_t *depth_rank, int64_t n, int n_samples, int64_t ld,
+                   const uint8_t *pair, const int64_t *chain_off, int n_chain, const double *logT, const double *logI,
+                   const double *logE, int n_depth, int8_t *state, double *omega);
+
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in
    the reference) extracts for sample column `sample_index`: CHROM, POS, the GT text as written, the first three
@@ -457,7 +482,8 @@ int snpm_cross_calls(snpm_ctx *ctx, const uint8_t *gt_codes, int64_t n, int n_sa
    use the generic reader. */
 typedef struct snpm_vcf snpm_vcf;
 int snpm_vcf_parse(const char *path, int sample_index, snpm_vcf **out);
-/* flags: bit 0 some FORMAT has GT, bit 1 some record has PL, bit 2 some record has INFO/DP, bit 3 CHROM / GT text is pure ASCII */
+/* flags: bit 0 some FORMAT has GT, bit 1 some record has PL, bit 2 some record has INFO/DP, bit 3 CHROM / GT text is pure ASCII,
+   bit 4 some FORMAT has DP (snpm_vcf_parse_calls_dp only) */
 int snpm_vcf_dims(const snpm_vcf *vcf, int64_t *n_records, int *chr_width, int *gt_width, int *flags, int *n_samples);
 /* chr [n * chr_width] and gt [n * gt_width]: NUL-padded fixed-width bytes; pos [n]; pl [n * 3]; dp [n] */
 int snpm_vcf_fill(const snpm_vcf *vcf, char *chr, int64_t *pos, char *gt, double *pl, int64_t *dp);
@@ -475,6 +501,12 @@ int snpm_vcf_free(snpm_vcf *vcf);
    codes [n, ld] (ld >= n_samples, the samples of a record contiguous; bytes past n_samples are left alone). */
 int snpm_vcf_parse_calls(const char *path, snpm_vcf **out);
 int snpm_vcf_fill_calls(const snpm_vcf *vcf, uint32_t *chr, int64_t *pos, uint8_t *codes, int64_t ld);
+/* snpm_vcf_parse_calls that also keeps the FORMAT DP subfield of every sample column (genotype_cross_hmm): the same records,
+   codes and refusals; snpm_vcf_dims reports flag bit 4 when some FORMAT carries DP.  snpm_vcf_fill_calls_dp writes dp [n, ld]
+   (ld >= n_samples): the integer as written, -1 for '.', for an entry that ends before its DP subfield and for a FORMAT without
+   DP (scikit-allel's fill value).  A DP text that is not a plain integer of at most 9 digits declines the file. */
+int snpm_vcf_parse_calls_dp(const char *path, snpm_vcf **out);
+int snpm_vcf_fill_calls_dp(const snpm_vcf *vcf, int32_t *dp, int64_t ld);
 
 /* ---------------------------------------------------------------- DB input: the reference's HDF5 files (host only, no GPU) */
 /* A reader for the files the reference keeps its DBs in -- `snps` int8 [num_snps, num_accessions] in lzf chunks of (1000,

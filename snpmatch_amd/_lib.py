@@ -48,6 +48,7 @@ SYMBOLS = [
     "snpm_h5_open", "snpm_h5_close", "snpm_h5_last_error", "snpm_h5_list", "snpm_h5_info", "snpm_h5_attr_name", "snpm_h5_read",
     "snpm_h5_read_rows", "snpm_panel_load_h5",
     "snpm_cross_calls", "snpm_vcf_parse_calls", "snpm_vcf_fill_calls",
+    "snpm_cross_hmm", "snpm_vcf_parse_calls_dp", "snpm_vcf_fill_calls_dp",
 ]
 
 _lib = None
@@ -235,6 +236,9 @@ def load():
     lib.snpm_vcf_parse_calls.argtypes = [C.c_char_p, pp]
     lib.snpm_vcf_fill_calls.argtypes = [p, p, p, p, i64]
     lib.snpm_cross_calls.argtypes = [p, p, i64, ci, i64, p, p, p, ci, dbl, ci, p, p]
+    lib.snpm_vcf_parse_calls_dp.argtypes = [C.c_char_p, pp]
+    lib.snpm_vcf_fill_calls_dp.argtypes = [p, p, i64]
+    lib.snpm_cross_hmm.argtypes = [p, p, p, i64, ci, i64, p, p, ci, p, p, p, ci, p, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]
     lib.snpm_profile_enable.argtypes = [p, ci]
     lib.snpm_profile_reset.argtypes = [p]
@@ -341,12 +345,13 @@ def vcf_parse(path, sample_index=0):
             "has_gt": bool(flags.value & 1), "has_pl": bool(flags.value & 2), "has_dp": bool(flags.value & 4)}
 
 
-def vcf_parse_calls(path):
+def vcf_parse_calls(path, depth=False):
     """native reader of EVERY sample column as call codes (snpm_vcf_parse_calls): dict with chr, pos, codes uint8 [n, n_samples]
-    and the sample names; None when the library declines the file (the caller then uses the Python reader)"""
+    and the sample names; None when the library declines the file (the caller then uses the Python reader).  ``depth``: also
+    ``dp`` int32 [n, n_samples], the FORMAT DP of every sample (-1 = absent), and ``has_dp`` (snpm_vcf_parse_calls_dp)"""
     lib = load()
     h = C.c_void_p()
-    rc = lib.snpm_vcf_parse_calls(os.fsencode(path), C.byref(h))
+    rc = (lib.snpm_vcf_parse_calls_dp if depth else lib.snpm_vcf_parse_calls)(os.fsencode(path), C.byref(h))
     if rc == SNPM_ERR_STATE:
         return None
     if rc != SNPM_OK:
@@ -363,9 +368,14 @@ def vcf_parse_calls(path):
             return None
         assert rc == SNPM_OK
         names = [lib.snpm_vcf_sample_name(h, i).decode() for i in range(ns)]
+        out = {"chr": chrom, "pos": pos, "codes": codes, "names": names, "has_gt": bool(flags.value & 1)}
+        if depth:
+            out["dp"] = np.empty((n, ns), dtype=np.int32)
+            out["has_dp"] = bool(flags.value & 16)
+            assert lib.snpm_vcf_fill_calls_dp(h, ptr(out["dp"]), ns) == SNPM_OK
     finally:
         lib.snpm_vcf_free(h)
-    return {"chr": chrom, "pos": pos, "codes": codes, "names": names, "has_gt": bool(flags.value & 1)}
+    return out
 
 
 def pack_rows_host(snps):

@@ -2,8 +2,9 @@
 Command line: ``snpmatch inbred``, ``snpmatch cross`` and ``snpmatch genotype_cross`` with the reference's flags
 (snpmatch/__init__.py:44-78), logging setup (:23-34) and exit codes (:155-183), plus ``makedb-native``
 to write the flat panel format this engine streams to the GPU.  ``genotype_cross`` serves the windowed likelihood-ratio
-mode with the parents named as two accessions of the database (``-p 6091x6191``); ``--hmm`` and ``-q / --father`` are
-refused with a message (core/genotype_cross.py says why).  The other reference subcommands (parser, pairsnp, makedb,
+mode with the parents named as two accessions of the database (``-p 6091x6191``); the HMM genotyper of the reference's
+``--hmm`` flag is the subcommand ``genotype_cross_hmm``.  ``--hmm`` itself and ``-q / --father`` are refused with a message
+(core/genotype_cross.py says why).  The other reference subcommands (parser, pairsnp, makedb,
 simulate) are outside the accelerated path.
 """
 import argparse
@@ -66,6 +67,14 @@ def snpmatch_genotype_cross(args):
     if not args['parents']:
         die("parents not specified: -p 6091x6191")
     genotype_cross.potatoCrossGenotyper(args)
+
+
+def snpmatch_genotype_cross_hmm(args):
+    from .core import genotype_cross
+    check_file(args['inFile'])
+    if not args['parents']:
+        die("parents not specified: -p 6091x6191")
+    genotype_cross.potatoCrossGenotyper(dict(args, hmm=True, father=None, binLen=0, lr_thres=None))
 
 
 def makedb_native(args):
@@ -135,6 +144,19 @@ def get_options(description, version_message):
     gcross.add_argument("-o", "--output", dest="outFile", default="genotype_cross", help="output file")
     gcross.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     gcross.set_defaults(func=snpmatch_genotype_cross)
+
+    ghmm = sub.add_parser('genotype_cross_hmm', help="Genotype F2 individuals of a cross marker by marker (AA / AB / BB) with a 3-state HMM")
+    ghmm.add_argument("-i", "--input_file", dest="inFile", help="multi-sample VCF file of the F2 individuals, DP in its FORMAT")
+    ghmm.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File",
+                      help="Path to SNP matrix: native flat panel directory (.snpm), .npz, or HDF5 chunked row-wise")
+    ghmm.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile",
+                      help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    ghmm.add_argument("-p", "--parents", dest="parents", help="Parents of the cross as two accessions of the database: 6091x6191")
+    ghmm.add_argument("--genome", dest="genome", default="athaliana_tair10",
+                      help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen, optionally recomb_rates)")
+    ghmm.add_argument("-o", "--output", dest="outFile", default="genotype_cross_hmm", help="output file")
+    ghmm.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    ghmm.set_defaults(func=snpmatch_genotype_cross_hmm)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -64,19 +64,36 @@ def _read_calls_native(path, sample):
     }
 
 
-def read_call_codes(path, native=True):
+def _sample_depth(keys, text):
+    """FORMAT DP of one sample column: the integer as written, -1 for '.', for an entry that ends before its DP subfield, for a
+    FORMAT without DP and for a text ``int`` does not take (scikit-allel's fill value)"""
+    for key, val in zip(keys, text.split(":")):
+        if key == "DP":
+            try:
+                return -1 if val == "." else int(val)
+            except ValueError:
+                return -1
+    return -1
+
+
+def read_call_codes(path, native=True, depth=False):
     """every sample column as call codes (``parsers.gt_call_code``): dict with samples, has_gt, chr, pos, codes uint8 [n, s].
     ``native``: the library's single-pass reader first (``snpm_vcf_parse_calls``); the loop below is the generic path and the
-    definition -- a sample column a record lacks, or a FORMAT without GT, reads './.' as in ``read_calls``."""
+    definition -- a sample column a record lacks, or a FORMAT without GT, reads './.' as in ``read_calls``.
+    ``depth``: also ``dp`` int32 [n, s], the FORMAT DP of every sample (``_sample_depth``; -1 also for a sample column the record
+    lacks), and ``has_dp``: some FORMAT carries DP (``snpm_vcf_parse_calls_dp`` / the same loop)."""
     if native:
         from .. import _lib
-        raw = _lib.vcf_parse_calls(path)
+        raw = _lib.vcf_parse_calls(path, depth=depth)
         if raw is not None:
-            return {"samples": np.array(raw["names"], dtype="U"), "has_gt": raw["has_gt"] or len(raw["pos"]) == 0,
-                    "chr": raw["chr"], "pos": raw["pos"], "codes": raw["codes"]}
+            out = {"samples": np.array(raw["names"], dtype="U"), "has_gt": raw["has_gt"] or len(raw["pos"]) == 0,
+                   "chr": raw["chr"], "pos": raw["pos"], "codes": raw["codes"]}
+            if depth:
+                out["dp"], out["has_dp"] = raw["dp"], raw["has_dp"]
+            return out
     from .parsers import gt_call_code
-    names, chrom, pos, rows = [], [], [], []
-    any_gt = False
+    names, chrom, pos, rows, dps = [], [], [], [], []
+    any_gt = any_dp = False
     known = {}                                   # genotype text -> code: a file holds a handful of distinct texts
     missing = gt_call_code("./.")
     with _open(path) as fh:
@@ -92,18 +109,28 @@ def read_call_codes(path, native=True):
             pos.append(int(rec[1]))
             keys = rec[8].split(":") if len(rec) > 8 else []
             any_gt |= "GT" in keys
+            any_dp |= "DP" in keys
             row = bytearray([missing]) * len(names)
+            row_dp = [-1] * len(names)
             for s in range(min(len(names), len(rec) - 9)):
                 g = _sample_fields(keys, rec[9 + s])[0]
                 code = known.get(g)
                 if code is None:
                     code = known[g] = gt_call_code(g)
                 row[s] = code
+                if depth:
+                    row_dp[s] = _sample_depth(keys, rec[9 + s])
             rows.append(bytes(row))
+            if depth:
+                dps.append(row_dp)
     n = len(chrom)
     codes = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(n, len(names)).copy() if n else np.zeros((0, len(names)), dtype=np.uint8)
-    return {"samples": np.array(names, dtype="U"), "has_gt": any_gt or n == 0, "chr": np.array(chrom, dtype="U"),
-            "pos": np.array(pos, dtype=int), "codes": codes}
+    out = {"samples": np.array(names, dtype="U"), "has_gt": any_gt or n == 0, "chr": np.array(chrom, dtype="U"),
+           "pos": np.array(pos, dtype=int), "codes": codes}
+    if depth:
+        out["dp"] = np.array(dps, dtype=np.int32).reshape(n, len(names))
+        out["has_dp"] = any_dp
+    return out
 
 
 def _sample_count(path):

@@ -3,7 +3,7 @@
 (``1``), parent 2 (``2``) or undecided (``NA``)?  Output: an R/qtl CSV.
 
 Public surface follows the reference module ``snpmatch.core.genotype_cross`` (core/genotype_cross.py:21-49, :52-111, :184-249):
-``getWindowGenotype``, ``GenotypeCross`` (``get_segregating_snps_parents``, ``genotype_cross``, the static
+``getWindowGenotype``, ``GenotypeCross`` (``get_segregating_snps_parents``, ``genotype_cross``, ``genotype_cross_hmm``, the static
 ``get_window_genotype_gts`` and ``write_output_genotype_cross``; attributes ``commonSNPsCHR``, ``commonSNPsPOS``, ``snpsP1``,
 ``snpsP2``, ``p1_ix``, ``p2_ix``, ``window_size``) and ``potatoCrossGenotyper``.
 
@@ -13,8 +13,17 @@ intersected with the panel, the two parents are read at the matched rows, the ro
 ONE device call (``engine.cross_calls`` -> ``k_gcross``) counts and decides every (window, sample).  Only matched markers count in
 the reference, so intersecting first and filtering by "segregating" afterwards selects the same markers.
 
+``genotype_cross_hmm`` (core/genotype_cross.py:113-181 of the reference) labels every matched segregating marker of every F2
+individual AA / AB / BB (0 / 1 / 2) by a 3-state Viterbi per (sample, chromosome).  One chain is serial; a job is samples x
+chromosomes chains that walk the same markers, so they run side by side: the host builds the tables of logarithms with numpy
+(``core.infer``), ONE device call (``engine.cross_hmm`` -> ``k_ghmm``, one lane per chain) returns every path.  It differs from
+the reference in three places: a genome chromosome without matched markers contributes no lines (the reference divides by
+zero), chromosome names are compared as bare ids (the reference compares ``genome.chrs`` with ``chrs_ids`` and finds nothing
+when the JSON says ``Chr1``), and a chromosome whose recombination fraction per marker exceeds 1 (a handful of markers on a very
+long chromosome: the transition matrix turns negative) is refused instead of carried through as NaN.
+
 Refused, with a message:
-  * ``--hmm`` (``genotype_cross_hmm``): a serial Viterbi per sample and chromosome, a different workload;
+  * ``--hmm`` of the ``genotype_cross`` subcommand: the HMM genotyper is the subcommand ``genotype_cross_hmm``;
   * ``-q / --father`` (parents from two VCF files): that branch of the reference indexes per-chromosome subsets into whole-file
     arrays (:73-82) and is only self-consistent for one chromosome with identical position sets;
   * genotypes without a separator (haploid calls): the reference's "unable to parse the format of GT in vcf!";
@@ -26,13 +35,15 @@ import logging
 import numpy as np
 
 from . import genomes
+from . import infer
 from . import parsers
 from . import snp_genotype
 from .. import engine
 
 log = logging.getLogger(__name__)
 
-HMM_REFUSED = "--hmm (the HMM genotyper) is not provided by this package: it is a serial Viterbi per sample, run it with the reference toolkit"
+HMM_REFUSED = ("--hmm is not provided by this package as a flag of genotype_cross: "
+               "the HMM genotyper is its own subcommand, genotype_cross_hmm (same -i / -d / -e / -p / --genome / -o)")
 FATHER_REFUSED = ("-q / --father (parents from two VCF files) is not provided by this package: "
                   "name the parents as two accessions of the database, -p 6091x6191")
 genome = None                        # set by potatoCrossGenotyper, as in the reference (a module global there too)
@@ -90,6 +101,12 @@ def count_and_decide(codes, p1, p2, win_off, lr_thres):
     return engine.cross_calls(engine.default_context(), codes, p1, p2, win_off, lr_thres)
 
 
+def viterbi_paths(codes, depth_rank, pair, chain_off, logT, logI, logE):
+    """int8 [n, n_samples] states (0 AA, 1 AB, 2 BB) of every (chain, sample): the one step of ``genotype_cross_hmm`` that runs on
+    the device.  Tests of the host side replace this function by a numpy twin."""
+    return engine.cross_hmm(engine.default_context(), codes, depth_rank, pair, chain_off, logT, logI, logE)
+
+
 class GenotypeCross(object):
 
     def __init__(self, g, parents, binLen=0, father=None, logDebug=True):
@@ -129,8 +146,96 @@ class GenotypeCross(object):
     snpsP1 = property(lambda self: self._whole_panel()[2])
     snpsP2 = property(lambda self: self._whole_panel()[3])
 
+    def _panel_chromosomes(self, db_rows):
+        """the panel's chromosome name of every row in ``db_rows``"""
+        inner = getattr(self.g, "g", None)
+        if inner is not None and hasattr(inner, "chr_regions") and hasattr(inner, "chrs"):
+            ends = np.asarray(inner.chr_regions)[:, 1]
+            return np.asarray(inner.chrs).astype('U')[np.searchsorted(ends, db_rows, side="right")]
+        return np.asarray(self.g.g_acc.chromosomes)[db_rows].astype('U')
+
     def genotype_cross_hmm(self, input_file, min_na_per_sample=0.8):
-        die(HMM_REFUSED)
+        """lines of the R/qtl CSV: two header lines, then one line per matched segregating marker, ``chr:pos,chr,cM,<state per
+        kept sample>`` (0 AA, 1 AB, 2 BB).  Samples whose share of markers with DP <= 0 reaches ``min_na_per_sample`` are dropped."""
+        the_genome = genome
+        assert the_genome is not None, "set genotype_cross.genome (potatoCrossGenotyper does) before genotyping"
+        log.info("loading input files!")
+        vcf = parsers.import_vcf_calls(input_file, self.logDebug, depth=True)
+        samples, codes, depth = np.asarray(vcf['samples']), vcf['codes'], vcf['calldata/DP']
+        if np.any(codes == parsers.GT_NO_SEPARATOR):
+            die("unable to parse the format of GT in vcf!")
+        vcf_chr, vcf_pos = np.asarray(vcf['chr']), np.asarray(vcf['pos'], dtype=np.int64)
+        chr_ids = genomes._bare(vcf_chr) if len(vcf_chr) else np.zeros(0, dtype="U1")
+        the_genome._check(np.unique(chr_ids), "given SNPs")
+        for cid in np.unique(chr_ids):
+            if cid not in the_genome.chrs_ids:
+                raise ValueError("%s: chromosome %s is not in the genome (%s)" % (input_file, cid, ", ".join(the_genome.chrs_ids)))
+            here = vcf_pos[chr_ids == cid]
+            if len(here) > 1 and np.any(here[1:] <= here[:-1]):
+                dup = np.any(here[1:] == here[:-1])
+                raise ValueError("%s: chromosome %s holds %s; genotype_cross_hmm needs every position once, in increasing order"
+                                 % (input_file, cid, "a position more than once" if dup else "positions out of order"))
+        db_rows, vcf_rows = self._matched_rows(vcf_chr, vcf_pos)
+        db_rows, vcf_rows = np.asarray(db_rows), np.asarray(vcf_rows)
+        p1, p2 = self._parent_calls(db_rows)
+        keep = np.flatnonzero((p1 != p2) & (p1 >= 0) & (p2 >= 0))
+        log.info("number of segregating snps between parents among the %d matched positions: %d", len(db_rows), len(keep))
+        if len(keep) == 0:
+            die("no marker of the VCF is a position of the database at which the parents differ: nothing to genotype")
+        db_rows, vcf_rows, p1, p2 = db_rows[keep], vcf_rows[keep], p1[keep], p2[keep]
+        if max(int(p1.max()), int(p2.max())) > 2:
+            raise ValueError("a parent carries call codes other than -1 / 0 / 1 / 2 at %d of the matched markers: genotype_cross_hmm "
+                             "models parental calls 0 / 1 / 2 only" % int(np.count_nonzero((p1 > 2) | (p2 > 2))))
+        num_markers = len(keep)
+        depth = depth[vcf_rows]
+        low = (depth <= 0).sum(axis=0) / float(num_markers)
+        good = np.where(low < min_na_per_sample)[0]
+        log.info("filtering %s samples due to very low number of informative markers" % str(len(samples) - len(good)))
+        samples = samples[good]
+        halved = depth[:, good] / 2
+        levels, rank = np.unique(np.rint(halved), return_inverse=True)
+        if len(levels) > 65536:
+            raise ValueError("more than 65536 distinct rounded depths in %s" % input_file)
+        rank = np.asarray(rank).reshape(halved.shape).astype(np.uint16)
+        if "recomb_rates" in the_genome.json.keys():
+            mean_recomb_rates = np.mean(np.array(the_genome.json['recomb_rates']))
+        else:
+            log.warning("Average recombination rates were missing in genome file. Add rates for each chromosome as an array in genome json file under 'recomb_rates' key. Using default rate of 3.5")
+            mean_recomb_rates = 3.5
+
+        # one chain per genome chromosome, its markers in panel order; the lines keep the panel's order of chromosomes
+        names = self._panel_chromosomes(db_rows)
+        positions = np.asarray(self.g.g_acc.positions)[db_rows]
+        marker_ids = genomes._bare(names)
+        unknown = np.setdiff1d(np.unique(marker_ids), the_genome.chrs_ids)
+        if len(unknown):
+            raise ValueError("the database names chromosome(s) %s, which the genome does not hold" % ", ".join(unknown))
+        order, chain_off, logT = [], [0], []
+        for cid, length in zip(the_genome.chrs_ids, the_genome.chrlen):
+            mine = np.flatnonzero(marker_ids == cid)
+            order.append(mine)
+            chain_off.append(chain_off[-1] + len(mine))
+            log_t = np.zeros((3, 3))
+            if len(mine) >= 2:               # (a chain of one marker takes no step; none at all: no lines, where the reference divides by zero)
+                log_t = infer.log_transition(infer._transition_frame(length / 1000000, len(mine), mean_recomb_rates).values)
+                if np.isnan(log_t).any():
+                    raise ValueError("chromosome %s: %d markers on %d bp at %s cM/Mb give a recombination fraction above 1 per marker; "
+                                     "its transition matrix has negative entries" % (cid, len(mine), int(length), mean_recomb_rates))
+            logT.append(log_t)
+        order = np.concatenate(order)
+        _, logI, logE = infer.emission_tables(levels, 0.036)
+        state = viterbi_paths(np.ascontiguousarray(codes[vcf_rows[order]][:, good]), np.ascontiguousarray(rank[order]),
+                              infer.pair_index(p1[order], p2[order]), np.array(chain_off, dtype=np.int64), np.array(logT), logI, logE)
+        in_panel_order = np.empty_like(state)
+        in_panel_order[order] = state
+
+        lines = ['id,,,' + ",".join(str(s) for s in samples), 'pheno,,' + ',0' * len(samples)]
+        text = np.array(["0", "1", "2"])
+        for k in range(num_markers):
+            cm = the_genome.estimated_cM_distance("%s,%s" % (names[k], positions[k]))
+            lines.append("%s:%s,%s,%s,%s" % (names[k], positions[k], names[k], cm, ",".join(text[in_panel_order[k]])))
+        log.info("done!")
+        return np.array(lines, dtype=str)
 
     @staticmethod
     def get_window_genotype_gts(input_gt, snpsP1_gt, snpsP2_gt, lr_thres):
@@ -246,8 +351,6 @@ class GenotypeCross(object):
 def potatoCrossGenotyper(args):
     """entry point of ``snpmatch genotype_cross``"""
     global genome
-    if args.get('hmm'):
-        die(HMM_REFUSED)
     if args.get('father') is not None:
         die(FATHER_REFUSED)
     genome = genomes.Genome(args['genome'])
@@ -255,5 +358,8 @@ def potatoCrossGenotyper(args):
     g = snp_genotype.Genotype(args['hdf5File'], args['hdf5accFile'])
     log.info("done!")
     crossgenotyper = GenotypeCross(g, args['parents'], args['binLen'], args['father'], args['logDebug'])
-    outfile_str = crossgenotyper.genotype_cross(args['inFile'], args['lr_thres'])
+    if args.get('hmm'):
+        outfile_str = crossgenotyper.genotype_cross_hmm(args['inFile'])
+    else:
+        outfile_str = crossgenotyper.genotype_cross(args['inFile'], args['lr_thres'])
     crossgenotyper.write_output_genotype_cross(outfile_str, args['outFile'])

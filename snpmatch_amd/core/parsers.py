@@ -428,14 +428,21 @@ def import_vcf_file(inFile, logDebug=False, samples_to_load=[0], add_fields=None
     return out
 
 
-def import_vcf_calls(inFile, logDebug=False, native=True):
+def import_vcf_calls(inFile, logDebug=False, native=True, depth=False):
     """Every sample column of a VCF as call codes (``gt_call_code``), without the genotype text matrix: dict with 'samples',
     'chr', 'pos' and 'codes' uint8 [n_records, n_samples].  The library's single-pass reader serves it; the Python reader takes
-    the files it declines (``native`` False: always).  What ``genotype_cross`` reads its F2 population with."""
-    calls = _vcf.read_call_codes(inFile, native=native)
+    the files it declines (``native`` False: always).  What ``genotype_cross`` reads its F2 population with.
+    ``depth``: also 'calldata/DP' int32 [n_records, n_samples], the FORMAT DP of every sample with scikit-allel's fill value -1
+    where it is absent (what ``genotype_cross_hmm`` reads); a file whose FORMAT never carries DP is refused."""
+    calls = _vcf.read_call_codes(inFile, native=native, depth=depth)
     if not calls["has_gt"]:
         die("input VCF file doesnt have required GT field")
-    return {'samples': calls["samples"], 'chr': calls["chr"], 'pos': calls["pos"], 'codes': calls["codes"]}
+    out = {'samples': calls["samples"], 'chr': calls["chr"], 'pos': calls["pos"], 'codes': calls["codes"]}
+    if depth:
+        if not calls["has_dp"] and len(calls["pos"]):
+            die("input VCF file doesnt carry DP in any FORMAT: genotype_cross_hmm needs the depth of every sample call")
+        out['calldata/DP'] = calls["dp"]
+    return out
 
 
 def potatoParser(inFile, logDebug, outFile="parser"):

@@ -32,6 +32,7 @@
 //   k_likelihood  likeliTest + nanmin + ratio on device (core/snpmatch.py:40-55,106-117).
 //   k_binom_identity  np_test_identity (core/snpmatch.py:57-72).   k_segregating  --refine support.
 //   k_gcross   genotype_cross: m1 / mh / m2 counts per (window, F2 sample) and the three-way likelihood decision (core/genotype_cross.py:21-49).
+//   k_ghmm     genotype_cross_hmm: the 3-state Viterbi path of every (chromosome, F2 sample), one chain per lane, tables of logarithms from the host (core/infer.py:17-58).
 //   k_f1_*     in-silico F1 scores in numpy's summation order (core/csmatch.py:115-125).
 //   k_build_lut, k_repitch_canon / k_pack_rows / k_unpack_rows (upload / download), k_pack_transpose[_packed]
 //   (accession-major copies), k_synth* / k_synth_sample (benchmark data), k_check_rows, k_expand_codes, k_seg_pack,
@@ -49,5 +50,6 @@
 #include "snpm_k_shared.hpp"      // k_sh_*: the shared-row scan of a batch (int8 MFMA contraction of fixed-point weight digits with the one-hot panel)
 #include "snpm_k_post.hpp"        // k_likelihood, k_binom_identity, k_segregating, k_f1_*, k_once_pack
 #include "snpm_k_gcross.hpp"      // k_gcross (genotype_cross: per window and sample parental calls)
+#include "snpm_k_ghmm.hpp"        // k_ghmm (genotype_cross_hmm: one Viterbi chain per lane)
 #include "snpm_k_io.hpp"          // k_pack_rows, k_repitch_canon, k_unpack_rows, k_synth*, k_calib_read
 #include "snpm_kernels_single.hpp"   // k_strict_single (panels of one accession: numpy's pairwise order)

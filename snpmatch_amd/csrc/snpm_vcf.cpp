@@ -40,6 +40,8 @@ struct VcfChunk {
     // every sample column as one call code per record (snpm_vcf_parse_calls): n * ncol bytes; ncol = sample columns of the block's
     // records (-1: none seen yet), uniform = every record of the block has that many
     std::vector<uint8_t> codes;
+    std::vector<int32_t> sample_dp;           // snpm_vcf_parse_calls_dp: the FORMAT DP of every sample column, n * ncol (-1 = absent)
+    bool any_fdp = false;                     // some FORMAT of the block carries DP
     long ncol = -1;
     bool uniform = true;
 };
@@ -52,6 +54,7 @@ struct snpm_vcf {
     size_t chr_width = 1, gt_width = 1;
     bool any_gt = false, any_pl = false, any_dp = false, ascii = true;
     bool calls = false;                       // parsed by snpm_vcf_parse_calls: the chunks hold call codes of every sample, no GT text / PL
+    bool calls_dp = false, any_fdp = false;   // parsed by snpm_vcf_parse_calls_dp: the chunks also hold every sample's FORMAT DP
 };
 
 namespace {
@@ -132,14 +135,14 @@ inline uint8_t gt_call_code(const char *p, size_t n)
     return hi | 4;
 }
 
-// every line of [s, end) into the chunk; sample_index -1: every sample column, as call codes
+// every line of [s, end) into the chunk; sample_index -1: every sample column, as call codes; -2: and every sample's FORMAT DP
 static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_index)
 {
     constexpr int MAXF = 4096;
     std::vector<Field> f(MAXF);
     Field keys[64], vals[64], nums[4];
     bool ok = true;
-    const bool all = sample_index < 0;
+    const bool all = sample_index < 0, with_dp = sample_index == -2;
     while (s < end && ok) {
         const char *nl = (const char *)memchr(s, '\n', (size_t)(end - s));
         const char *e = nl ? nl : end;
@@ -191,6 +194,7 @@ static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_
             if (nk == 64) { ok = false; break; }
             for (int k = 0; k < nk; ++k)
                 if (keys[k].n == 2 && keys[k].p[0] == 'G' && keys[k].p[1] == 'T') v->any_gt = true;
+                else if (with_dp && keys[k].n == 2 && keys[k].p[0] == 'D' && keys[k].p[1] == 'P') v->any_fdp = true;
             if (all) {
                 // the GT entry of every sample column ('./.' where the column has none, a bare '.' is './.': _vcf._sample_fields)
                 const long ncol = nf - 9;
@@ -201,10 +205,18 @@ static void parse_block(VcfChunk *v, const char *s, const char *end, int sample_
                     if (nv == 64) { ok = false; break; }
                     const int m = nk < nv ? nk : nv;
                     uint8_t code = 3;
-                    for (int k = 0; k < m; ++k)
+                    int64_t sdp = -1;
+                    for (int k = 0; k < m; ++k) {
                         if (keys[k].n == 2 && keys[k].p[0] == 'G' && keys[k].p[1] == 'T')
                             code = (vals[k].n == 1 && vals[k].p[0] == '.') ? 3 : gt_call_code(vals[k].p, vals[k].n);
+                        else if (with_dp && keys[k].n == 2 && keys[k].p[0] == 'D' && keys[k].p[1] == 'P') {
+                            if (vals[k].n == 1 && vals[k].p[0] == '.') sdp = -1;
+                            else if (vals[k].n > 9 || !parse_int(vals[k].p, vals[k].n, &sdp)) ok = false;    // int() may still accept it: the generic reader decides
+                        }
+                    }
+                    if (!ok) break;
                     v->codes.push_back(code);
+                    if (with_dp) v->sample_dp.push_back((int32_t)sdp);
                 }
                 if (!ok) break;
             } else if (nf > 9 + sample_index) {
@@ -322,7 +334,7 @@ static void for_each_chunk(const snpm_vcf *v, const std::function<void(const Vcf
 
 static int vcf_parse_impl(const char *path, int sample_index, snpm_vcf **out)
 try {
-    if (!path || !out || sample_index < -1 || sample_index > 4000) return SNPM_ERR_BADARG;
+    if (!path || !out || sample_index < -2 || sample_index > 4000) return SNPM_ERR_BADARG;
     std::unique_ptr<snpm_vcf> v(new snpm_vcf());
     gzFile gz = gzopen(path, "rb");          // transparently reads plain text as well
     if (!gz) return SNPM_ERR_BADARG;
@@ -523,6 +535,7 @@ try {
         v->any_gt |= ch->any_gt;
         v->any_pl |= ch->any_pl;
         v->any_dp |= ch->any_dp;
+        v->any_fdp |= ch->any_fdp;
         v->ascii &= ch->ascii;
         if (ch->has_names) v->sample_names = ch->sample_names;      // the last #CHROM line of the file, as before
     }
@@ -530,6 +543,7 @@ try {
     if (sample_index < 0) {
         // every record must carry exactly the sample columns the header names: anything else is the generic reader's to interpret
         v->calls = true;
+        v->calls_dp = sample_index == -2;
         for (const auto &ch : v->chunks)
             if (!ch->pos.empty() && (!ch->uniform || ch->ncol != (long)v->sample_names.size())) return SNPM_ERR_STATE;
     }
@@ -546,6 +560,24 @@ int snpm_vcf_parse(const char *path, int sample_index, snpm_vcf **out)
 }
 
 int snpm_vcf_parse_calls(const char *path, snpm_vcf **out) { return vcf_parse_impl(path, -1, out); }
+
+int snpm_vcf_parse_calls_dp(const char *path, snpm_vcf **out) { return vcf_parse_impl(path, -2, out); }
+
+// dp [n, ld]: the FORMAT DP of every sample column (-1 = absent), the samples of a record contiguous
+int snpm_vcf_fill_calls_dp(const snpm_vcf *v, int32_t *dp, int64_t ld)
+try {
+    if (!v || !v->calls_dp || !dp) return SNPM_ERR_BADARG;
+    const size_t ns = v->sample_names.size();
+    if (ld < (int64_t)ns) return SNPM_ERR_BADARG;
+    if (ns == 0) return SNPM_OK;
+    for_each_chunk(v, [&](const VcfChunk &c, size_t r0) {
+        const size_t n = c.pos.size();
+        for (size_t i = 0; i < n; ++i) memcpy(dp + (r0 + i) * (size_t)ld, c.sample_dp.data() + i * ns, ns * sizeof(int32_t));
+    });
+    return SNPM_OK;
+} catch (...) {
+    return SNPM_ERR_STATE;
+}
 
 // chr [n * chr_width] as UTF-32 (as snpm_vcf_fill_u32), pos [n], codes [n, ld] with the samples of a record contiguous
 int snpm_vcf_fill_calls(const snpm_vcf *v, uint32_t *chr, int64_t *pos, uint8_t *codes, int64_t ld)
@@ -579,7 +611,7 @@ int snpm_vcf_dims(const snpm_vcf *v, int64_t *n_records, int *chr_width, int *gt
     if (n_records) *n_records = (int64_t)v->n;
     if (chr_width) *chr_width = (int)v->chr_width;
     if (gt_width) *gt_width = (int)v->gt_width;
-    if (flags) *flags = (v->any_gt ? 1 : 0) | (v->any_pl ? 2 : 0) | (v->any_dp ? 4 : 0) | (v->ascii ? 8 : 0);
+    if (flags) *flags = (v->any_gt ? 1 : 0) | (v->any_pl ? 2 : 0) | (v->any_dp ? 4 : 0) | (v->ascii ? 8 : 0) | (v->any_fdp ? 16 : 0);
     if (n_samples) *n_samples = (int)v->sample_names.size();
     return SNPM_OK;
 }

@@ -665,6 +665,41 @@ def cross_calls(ctx, codes, p1, p2, win_off, lr_thres, n_marker_thres=5, return_
     return (geno, counts) if return_counts else geno
 
 
+def cross_hmm(ctx, codes, depth_rank, pair, chain_off, logT, logI, logE, return_omega=False):
+    """genotype_cross_hmm in one device call (``snpm_cross_hmm``): the 3-state Viterbi path of every (chain, sample).  ``codes``
+    uint8 and ``depth_rank`` uint16, both [n, n_samples] (markers chain by chain; row-strided views with one common stride
+    travel as they are), ``pair`` [n] the ordered parental pair 0..5, ``chain_off`` [n_chain + 1], ``logT`` [n_chain, 3, 3],
+    ``logI`` / ``logE`` [6, n_depth, 4, 3] (``core.infer`` builds them with numpy).  Returns ``state`` int8 [n, n_samples] and, with
+    ``return_omega``, also float64 [n, n_samples, 3].  ``ctx`` None: the library only validates."""
+    codes, depth_rank = np.asarray(codes), np.asarray(depth_rank)
+    assert codes.ndim == 2 and codes.dtype == np.uint8, "codes: uint8 [n, n_samples]"
+    assert depth_rank.shape == codes.shape and depth_rank.dtype == np.uint16, "depth_rank: uint16 of the shape of codes"
+    n, ns = codes.shape
+    if (n > 1 and ns > 0 and codes.strides[1] == 1 and depth_rank.strides[1] == 2 and codes.strides[0] >= ns
+            and depth_rank.strides[0] == 2 * codes.strides[0]):
+        ld = codes.strides[0]               # rows with padding behind them travel as they are
+    else:
+        codes, depth_rank, ld = np.ascontiguousarray(codes), np.ascontiguousarray(depth_rank), ns
+    pair = np.ascontiguousarray(pair, dtype=np.uint8)
+    assert len(pair) == n, "one parental pair per marker"
+    chain_off = np.ascontiguousarray(chain_off, dtype=np.int64)
+    n_chain = len(chain_off) - 1
+    assert n_chain >= 0, "chain_off holds n_chain + 1 entries"
+    logT = np.ascontiguousarray(logT, dtype=np.float64)
+    logI = np.ascontiguousarray(logI, dtype=np.float64)
+    logE = np.ascontiguousarray(logE, dtype=np.float64)
+    assert logT.shape == (n_chain, 3, 3), "logT: [n_chain, 3, 3]"
+    assert logI.ndim == 4 and logI.shape[0] == 6 and logI.shape[2:] == (4, 3) and logE.shape == logI.shape, "logI / logE: [6, n_depth, 4, 3]"
+    n_depth = logI.shape[1]
+    state = np.empty((n, ns), dtype=np.int8)
+    omega = np.empty((n, ns, 3), dtype=np.float64) if return_omega else None
+    lib = ctx.lib if ctx is not None else _lib.load()
+    h = ctx.h if ctx is not None else None
+    check(lib.snpm_cross_hmm(h, ptr(codes), ptr(depth_rank), n, ns, ld, ptr(pair), ptr(chain_off), n_chain, ptr(logT), ptr(logI),
+                             ptr(logE), n_depth, ptr(state), ptr(omega)), h)
+    return (state, omega) if return_omega else state
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the
