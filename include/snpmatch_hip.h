@@ -428,7 +428,8 @@ int snpm_query_f1_pairs(snpm_query *query, const int32_t *acc_idx, int n_sel, do
 int snpm_debug_stream_read(snpm_panel *panel, int64_t *bytes_read);
 int snpm_profile_enable(snpm_ctx *ctx, int on);
 int snpm_profile_reset(snpm_ctx *ctx);
-/* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm".  Synchronises the stream. */
+/* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t" (transpose of
+   snpm_pair_counts), "pairs_c" (its count).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -472,6 +473,26 @@ int snpm_cross_calls(snpm_ctx *ctx, const uint8_t *gt_codes, int64_t n, int n_sa
 int snpm_cross_hmm(snpm_ctx *ctx, const uint8_t *gt_codes, const uint16_t *depth_rank, int64_t n, int n_samples, int64_t ld,
                    const uint8_t *pair, const int64_t *chain_off, int n_chain, const double *logT, const double *logI,
                    const double *logE, int n_depth, int8_t *state, double *omega);
+
+/* ---------------------------------------------------------------- pairsnp */
+/* snpmatch.pairwiseScore (core/snpmatch.py:270-309 of the reference: two sample files, a Python loop over chromosomes) for EVERY
+   pair of a set of samples as ONE device call.  Host pointers in and out.
+     ids [n, ld]        one byte per (record, sample), the samples of a record contiguous, ld >= n_samples: 0 = the sample has no
+                        call at this record, 1..127 = the id of its genotype text (equal texts, equal ids)
+     seg_off [n_seg+1]  record range of every segment (a chromosome): 0 = seg_off[0] <= ... <= seg_off[n_seg] = n
+     common [n_seg, n_samples, n_samples]   common[s][a][b] = records r of segment s with ids[r][a] != 0 && ids[r][b] != 0
+     match  [n_seg, n_samples, n_samples]   match[s][a][b]  = records r of segment s with ids[r][a] == ids[r][b] != 0
+   Both are full symmetric matrices of exact int32 counts; the diagonal of either is the number of calls of the sample in the
+   segment.  Limits: n_samples <= SNPM_PAIR_MAX_SAMPLES, n_seg * n_samples^2 <= SNPM_PAIR_MAX_CELLS (512 MiB per result matrix), a
+   segment of 2^31 records or more is refused (its counts would not fit).
+   Every argument is validated on the host before the context or the device is touched (SNPM_ERR_BADARG with a message; with ctx ==
+   NULL the message is in snpm_last_error(NULL)): seg_off from 0 to n without a decrease, ld >= n_samples, every id inside the
+   first n_samples columns <= 127 (padding columns are not looked at and never reach the device), no negative size, the limits.
+   n_seg == 0 or n_samples == 0 return without a launch and write nothing; n == 0 with n_seg > 0 writes zeros without a launch. */
+#define SNPM_PAIR_MAX_SAMPLES 4096
+#define SNPM_PAIR_MAX_CELLS ((int64_t)1 << 27)
+int snpm_pair_counts(snpm_ctx *ctx, const uint8_t *ids, int64_t n, int n_samples, int64_t ld, const int64_t *seg_off, int n_seg,
+                     int32_t *common, int32_t *match);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

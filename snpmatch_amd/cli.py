@@ -4,8 +4,9 @@ Command line: ``snpmatch inbred``, ``snpmatch cross`` and ``snpmatch genotype_cr
 to write the flat panel format this engine streams to the GPU.  ``genotype_cross`` serves the windowed likelihood-ratio
 mode with the parents named as two accessions of the database (``-p 6091x6191``); the HMM genotyper of the reference's
 ``--hmm`` flag is the subcommand ``genotype_cross_hmm``.  ``--hmm`` itself and ``-q / --father`` are refused with a message
-(core/genotype_cross.py says why).  The other reference subcommands (parser, pairsnp, makedb,
-simulate) are outside the accelerated path.
+(core/genotype_cross.py says why).  ``pairsnp`` compares two sample files as the reference does; ``pairsnp-batch`` compares every
+pair of a cohort in one device call.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+path.
 """
 import argparse
 import logging
@@ -75,6 +76,20 @@ def snpmatch_genotype_cross_hmm(args):
     if not args['parents']:
         die("parents not specified: -p 6091x6191")
     genotype_cross.potatoCrossGenotyper(dict(args, hmm=True, father=None, binLen=0, lr_thres=None))
+
+
+def snpmatch_paircomparions(args):
+    from .core import snpmatch
+    check_file(args['inFile_1'])
+    check_file(args['inFile_2'])
+    snpmatch.pairwiseScore(args['inFile_1'], args['inFile_2'], args['logDebug'], args['outFile'], args['hdf5File'])
+
+
+def snpmatch_pair_cohort(args):
+    from .core import pairsnp
+    for f in args['inFiles']:
+        check_file(f)
+    pairsnp.potatoPairCohort(args)
 
 
 def makedb_native(args):
@@ -157,6 +172,25 @@ def get_options(description, version_message):
     ghmm.add_argument("-o", "--output", dest="outFile", default="genotype_cross_hmm", help="output file")
     ghmm.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     ghmm.set_defaults(func=snpmatch_genotype_cross_hmm)
+
+    pair = sub.add_parser('pairsnp', help="pairwise comparison of two snp files")
+    pair.add_argument("-i", "--input_file_1", dest="inFile_1", help="VCF/BED file for the variants in the sample one")
+    pair.add_argument("-j", "--input_file_2", dest="inFile_2", help="VCF/BED file for the variants in the sample two")
+    pair.add_argument("-d", "--hdf5_file", dest="hdf5File", default=None,
+                      help="Path to SNP matrix (as for inbred): only positions the database holds are compared")
+    pair.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    pair.add_argument("-o", "--output", dest="outFile", default="pairsnp", help="output json file")
+    pair.set_defaults(func=snpmatch_paircomparions)
+
+    # not in the reference (one process per pair of files): every pair of a plate or sequencing batch in ONE device call
+    pairs = sub.add_parser('pairsnp-batch', help="`pairsnp` for every pair of a cohort: one multi-sample VCF, or several files of one sample each")
+    pairs.add_argument("-i", "--input_files", dest="inFiles", nargs='+', required=True,
+                       help="one multi-sample VCF, or VCF/BED files of one sample each")
+    pairs.add_argument("-d", "--hdf5_file", dest="hdf5File", default=None,
+                       help="Path to SNP matrix (as for inbred): only positions the database holds are compared")
+    pairs.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    pairs.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pairs.tsv and <prefix>.pairs.npz")
+    pairs.set_defaults(func=snpmatch_pair_cohort)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

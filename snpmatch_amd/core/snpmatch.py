@@ -339,3 +339,9 @@ def potatoGenotyper(args):
     if args['refine']:
         job.filter_tophits()
     log.info("finished!")
+
+
+def pairwiseScore(inFile_1, inFile_2, logDebug, outFile=None, hdf5File=None):
+    """``snpmatch pairsnp`` (core/snpmatch.py:270-309): lives in ``core.pairsnp`` with its cohort form"""
+    from . import pairsnp
+    return pairsnp.pairwiseScore(inFile_1, inFile_2, logDebug, outFile, hdf5File)

@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c"};
 
 struct Buf {
     void *p = nullptr;
@@ -54,6 +54,8 @@ struct Buf {
     X(ws_gc_codes) X(ws_gc_par) X(ws_gc_off) X(ws_gc_geno) X(ws_gc_counts)      /* snpm_cross_calls (snpm_api_gcross.hpp) */      \
     /* snpm_cross_hmm (snpm_api_ghmm.hpp): codes, depth ranks, backpointers and states [n, pitch]; pair [n]; chain bounds; logT | logI | logE; omega */ \
     X(ws_gh_codes) X(ws_gh_depth) X(ws_gh_bp) X(ws_gh_state) X(ws_gh_pair) X(ws_gh_off) X(ws_gh_tab) X(ws_gh_omega)               \
+    /* snpm_pair_counts (snpm_api_pairs.hpp): ids [n, pitch]; sample-major planes [pitch, n_pad]; chunk table; common | match */  \
+    X(ws_pr_ids) X(ws_pr_planes) X(ws_pr_chunks) X(ws_pr_out)                                                                     \
     X(ws_once) X(ws_once_table)     /* snpm_genotype_once: its packed results (unfused form); the weight table of its coded form */ \
     X(ws_once_state)                /* {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls */             \
     /* segmented / batched scoring */                                                                                             \
@@ -618,6 +620,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_gcross.hpp"
 
 #include "snpm_api_ghmm.hpp"
+
+#include "snpm_api_pairs.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

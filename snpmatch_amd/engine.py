@@ -700,6 +700,35 @@ def cross_hmm(ctx, codes, depth_rank, pair, chain_off, logT, logI, logE, return_
     return (state, omega) if return_omega else state
 
 
+PAIR_MAX_ID = 127          # ids of ``pair_counts``: the high bit of every byte is free for the kernel's byte-parallel tests
+
+
+def pair_counts(ctx, ids, seg_off):
+    """pairsnp for every pair of a set of samples in one device call (``snpm_pair_counts``): ``ids`` uint8 [n, n_samples], 0 = the
+    sample has no call at the record, 1..127 = the id of its genotype text (a row-strided view such as ``m[:, :k]`` is passed as it
+    is), ``seg_off`` [n_seg + 1] the records of every segment (chromosome).  Returns ``(common, match)``, both int32 [n_seg,
+    n_samples, n_samples]: records both samples have a call at, and records at which the two calls are the same text.  ``ctx``
+    None: the library only validates (a sound call then fails for want of a context)."""
+    ids = np.asarray(ids)
+    assert ids.ndim == 2 and ids.dtype == np.uint8, "ids: uint8 [n, n_samples]"
+    n, ns = ids.shape
+    if n > 1 and ns > 0 and ids.strides[1] == 1 and ids.strides[0] >= ns:
+        ld = ids.strides[0]                 # rows with padding behind them travel as they are
+    else:
+        ids, ld = np.ascontiguousarray(ids), ns
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+    n_seg = len(seg_off) - 1
+    assert n_seg >= 0, "seg_off holds n_seg + 1 entries"
+    lib = ctx.lib if ctx is not None else _lib.load()
+    h = ctx.h if ctx is not None else None
+    if n_seg * ns * ns > (1 << 27):         # the library's limit, before numpy is asked for the result arrays
+        check(lib.snpm_pair_counts(h, ptr(ids), n, ns, ld, ptr(seg_off), n_seg, None, None), h)
+    common = np.empty((n_seg, ns, ns), dtype=np.int32)
+    match = np.empty((n_seg, ns, ns), dtype=np.int32)
+    check(lib.snpm_pair_counts(h, ptr(ids), n, ns, ld, ptr(seg_off), n_seg, ptr(common), ptr(match)), h)
+    return common, match
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the
