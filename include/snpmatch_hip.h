@@ -429,7 +429,8 @@ int snpm_debug_stream_read(snpm_panel *panel, int64_t *bytes_read);
 int snpm_profile_enable(snpm_ctx *ctx, int on);
 int snpm_profile_reset(snpm_ctx *ctx);
 /* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t" (transpose of
-   snpm_pair_counts), "pairs_c" (its count).  Synchronises the stream. */
+   snpm_pair_counts), "pairs_c" (its count), "kin_planes" / "kin_count" (the two kernels of snpm_panel_kinship_counts).
+   Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -493,6 +494,28 @@ int snpm_cross_hmm(snpm_ctx *ctx, const uint8_t *gt_codes, const uint16_t *depth
 #define SNPM_PAIR_MAX_CELLS ((int64_t)1 << 27)
 int snpm_pair_counts(snpm_ctx *ctx, const uint8_t *ids, int64_t n, int n_samples, int64_t ld, const int64_t *seg_off, int n_seg,
                      int32_t *common, int32_t *match);
+
+/* ---------------------------------------------------------------- panel kinship */
+/* Genotype.kinship_given_snps / calc_kinship_mat (core/snp_genotype.py:256-289, :440-459 of the reference: a Python loop over
+   1000-row chunks, two dense float products each) on the RESIDENT panel (int8 or packed), as one call.  Host pointers in and out.
+     cols [ncols]     accession columns of the panel, any order, repeats allowed (a repeat counts as listed); NULL = all
+                      accessions in panel order, ncols must then be the panel's accession count (or 0)
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows) (row0 is ignored
+                      when row_idx is given)
+     ninfo [ncols, ncols]   rows where both calls are not missing (hets and an int8 panel's "other" code included)
+     same  [ncols, ncols]   rows where both calls are homozygous (0 or 1) and equal
+     diff  [ncols, ncols]   rows where both calls are homozygous and different
+   All three are full symmetric matrices of exact int32 counts, the diagonal included; the reference's kinship is
+   (same - diff) / ninfo.  The row axis is processed in slabs whose bit-planes fit a workspace budget (512 MiB; SNPM_KIN_WS_MB,
+   read by snpm_init); the counts accumulate on the device.  Limits: ncols <= SNPM_KIN_MAX_ACCESSIONS (each result matrix stays
+   below 2^27 cells and the tile pairs of the count kernel below 2^16), n_rows < 2^31 (the counts are int32).
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message): no negative size, the limits, non-NULL
+   outputs when ncols > 0 -- these before the panel handle is looked at, the message of a NULL panel is in snpm_last_error(NULL)
+   -- then every column and row index inside the panel.  ncols == 0 returns without a launch and writes nothing; n_rows == 0
+   writes zeros without a launch.  Uploads into the panel that are still in flight are waited for on the device. */
+#define SNPM_KIN_MAX_ACCESSIONS 11552
+int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                              int32_t *ninfo, int32_t *same, int32_t *diff);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

@@ -5,7 +5,8 @@ to write the flat panel format this engine streams to the GPU.  ``genotype_cross
 mode with the parents named as two accessions of the database (``-p 6091x6191``); the HMM genotyper of the reference's
 ``--hmm`` flag is the subcommand ``genotype_cross_hmm``.  ``--hmm`` itself and ``-q / --father`` are refused with a message
 (core/genotype_cross.py says why).  ``pairsnp`` compares two sample files as the reference does; ``pairsnp-batch`` compares every
-pair of a cohort in one device call.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+pair of a cohort in one device call.  ``kinship`` (not in the reference as a command) counts the relatedness of every pair of
+accessions of the database on the device and lists the near-identical ones.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
 path.
 """
 import argparse
@@ -90,6 +91,14 @@ def snpmatch_pair_cohort(args):
     for f in args['inFiles']:
         check_file(f)
     pairsnp.potatoPairCohort(args)
+
+
+def snpmatch_kinship(args):
+    from .core import kinship
+    check_file(args['hdf5File'])
+    if args['accFile']:
+        check_file(args['accFile'])
+    kinship.potatoKinship(args)
 
 
 def makedb_native(args):
@@ -191,6 +200,20 @@ def get_options(description, version_message):
     pairs.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     pairs.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pairs.tsv and <prefix>.pairs.npz")
     pairs.set_defaults(func=snpmatch_pair_cohort)
+
+    # not in the reference as a command (its Genotype.kinship_given_snps is a method): relatedness of every pair of accessions of the DB
+    kin = sub.add_parser('kinship', help="kinship of every pair of accessions of the database, and the list of near-identical pairs")
+    kin.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    kin.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    kin.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    kin.add_argument("--bed", dest="bed", default=None, help="only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
+    kin.add_argument("--min_identity", dest="min_identity", default=0.99, type=float,
+                     help="list a pair as duplicates from this share of equal calls among the rows where both are homozygous (default 0.99)")
+    kin.add_argument("--min_sites", dest="min_sites", default=100, type=int,
+                     help="... and only when both are homozygous at this many rows or more (default 100)")
+    kin.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    kin.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.kinship.npz and <prefix>.duplicates.tsv")
+    kin.set_defaults(func=snpmatch_kinship)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -378,6 +378,56 @@ class Genotype(object):
             acc_ix = np.array([a for a in acc_ix if a is not None], dtype="int")
         return acc_ix
 
+    # ------------------------------------------------------------------ regions and relatedness
+    def get_chr_ind(self, echr):
+        """Which of the DB's chromosomes ``echr`` names ('Chr1', 'chr1' and '1' are one chromosome): its index, or None when
+        no chromosome, or more than one, carries that id."""
+        wanted = _bare_chr_id(echr)
+        matches = [k for k, name in enumerate(self.chrs.tolist()) if _bare_chr_id(name) == wanted]
+        return matches[0] if len(matches) == 1 else None
+
+    def determine_snp_ix_given_bed(self, req_bed):
+        """DB rows inside a region given as ``"Chr1,1,1000"`` or as a (chromosome, start, end) triple: the consecutive rows of
+        that chromosome from the first position >= start up to, not including, the first position >= end."""
+        fields = [f.strip() for f in req_bed.split(",")] if isinstance(req_bed, str) else list(req_bed)
+        if len(fields) != 3:
+            raise ValueError("a region is chromosome,start,end (Chr1,1,1000000): got %r" % (req_bed,))
+        name, lo, hi = fields[0], int(fields[1]), int(fields[2])
+        which = self.get_chr_ind(name)
+        assert which is not None, "chromosome %s is not in the database" % name
+        first, last = (int(v) for v in np.asarray(self.g.chr_regions)[which])
+        bounds = np.searchsorted(np.asarray(self.g.positions[first:last]), [lo, hi], side="left")
+        return np.arange(first + int(bounds[0]), first + int(bounds[1]))
+
+    def kinship_counts(self, filter_acc_ix=None, filter_snp_ix=None):
+        """(ninfo, same, diff) int32 [n, n] of the listed accessions over the listed DB rows, counted on the resident panel
+        (``engine.kinship_counts``): rows where both calls are informative, where both are homozygous and equal, where both are
+        homozygous and different.  None = all accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a
+        dense range."""
+        from .. import engine
+        panel = self.panel()
+        if getattr(self, "_shard", None) is not None or not isinstance(panel, engine.Panel):
+            raise TypeError("kinship needs every accession column of the DB on one device: this DB is %s.  Run it in one process on "
+                            "one GPU with a DB that fits it (SNPMATCH_GPUS unset or one device, no torch.distributed launcher)"
+                            % ("spread over several GPUs by accession" if isinstance(panel, engine.GroupPanel) or
+                               getattr(self, "_shard", None) is not None else "streamed through the device in row slabs"))
+        rows = None
+        if filter_snp_ix is not None:
+            rows = np.asarray(filter_snp_ix, dtype=np.int64).reshape(-1)
+            if len(rows) and rows[0] >= 0 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))):
+                rows = range(int(rows[0]), int(rows[0]) + len(rows))
+        return engine.kinship_counts(panel, filter_acc_ix, rows)
+
+    def kinship_given_snps(self, filter_acc_ix=None, filter_snp_ix=None):
+        """Kinship between all pairs of the listed accessions over the listed DB rows (core/snp_genotype.py:256-289): fp64 ndarray
+        ``(same - diff) / ninfo``, ``nan`` where a pair shares no informative row.  The reference sums ``calc_kinship_mat`` over
+        1000-row chunks -- sums of integers in fp64, exact -- and divides once: one division of the same two integers gives its
+        bits.  Two places where its method cannot be followed: with ``filter_acc_ix=None`` it indexes with ``[:, None]`` and fails
+        (here: all accessions); its line 272 replaces a given ``filter_snp_ix`` by ``arange(len)``, i.e. uses the FIRST ``len``
+        rows (here: the listed rows)."""
+        ninfo, same, diff = self.kinship_counts(filter_acc_ix, filter_snp_ix)
+        return kinship_from_counts(ninfo, same, diff)
+
     # ------------------------------------------------------------------ --refine support
     def identify_segregating_snps(self, accs_ix):
         """DB rows where the given accessions do not all carry the same informative call
@@ -408,6 +458,34 @@ class Genotype(object):
             hi = np.where(seen, firsts, 0).max(axis=0)
             return both[:, 0, :].any(axis=0) | (seen.any(axis=0) & (lo != hi))
         return panel.segregating_rows(accs_ix)                      # one device scan over the listed columns (k_segregating)
+
+
+def kinship_from_counts(ninfo, same, diff):
+    """(same - diff) / ninfo in fp64; 0 / 0 = nan, as ``np.divide`` of the reference's two matrices gives it"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.divide((np.asarray(same, dtype=np.int64) - np.asarray(diff, dtype=np.int64)).astype(np.float64),
+                         np.asarray(ninfo).astype(np.float64))
+
+
+def calc_kinship_mat(snp, return_counts=False):
+    """Kinship of a small SNP matrix [n_snp, n_acc] on the host, with the semantics of the reference's function of this name
+    (core/snp_genotype.py:440-459): a call >= 0 is informative; 0 counts as -1, 1 as +1, everything else (hets, missing) as 0.
+    ``return_counts``: the pair ``(score, informative)`` -- sum of the products (= same - diff) and informative rows per pair of
+    accessions, fp64 arrays of exact integers -- else their quotient.  Plain arrays where the reference returns matrices."""
+    calls = np.asarray(snp).T                                   # [n_acc, n_snp]
+    known = (calls >= 0).astype(np.float64)
+    informative = known @ known.T
+    signed = np.where(calls == 0, -1.0, np.where(calls == 1, 1.0, 0.0))
+    score = signed @ signed.T + 0.0                             # (+ 0.0: a sum of -0.0 products is a plain zero)
+    if return_counts:
+        return score, informative
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.divide(score, informative)
+
+
+def _bare_chr_id(name):
+    """'Chr1' / 'chr1' / '1' -> '1'"""
+    return re.sub("chr", "", str(name), flags=re.IGNORECASE)
 
 
 class _ChromosomeRows(object):

@@ -729,6 +729,45 @@ def pair_counts(ctx, ids, seg_off):
     return common, match
 
 
+KIN_MAX_ACCESSIONS = 11552     # SNPM_KIN_MAX_ACCESSIONS: columns of one ``kinship_counts`` call
+
+
+def kinship_counts(panel, cols=None, rows=None):
+    """Relatedness counts of every pair of accession columns of a resident panel in one device call
+    (``snpm_panel_kinship_counts``).  ``cols``: accession indices, any order, repeats allowed (None: all accessions); ``rows``: panel
+    rows as an index array, any order, repeats allowed, or a ``slice`` / ``range`` of step 1 (a dense range), or None (all rows).
+    Returns ``(ninfo, same, diff)``, int32 [n_cols, n_cols], full and symmetric: rows where both calls are not missing, rows where
+    both are homozygous and equal, rows where both are homozygous and different.  The reference's kinship is
+    ``(same - diff) / ninfo``.  Only a panel whose columns all live on one device can be asked: group (accession-sharded) and
+    streamed panels are refused."""
+    if not isinstance(panel, Panel):
+        raise TypeError("kinship_counts needs every accession column on one device: a %s is %s, load the DB as one resident "
+                        "panel (int8 or packed) on one GPU" % (type(panel).__name__, "spread over several GPUs by accession"
+                                                               if isinstance(panel, GroupPanel) else "not a resident panel"))
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row0, row_idx = 0, None
+    if rows is None:
+        n_rows = panel.n_snp
+    elif isinstance(rows, (slice, range)):
+        r = range(*rows.indices(panel.n_snp)) if isinstance(rows, slice) else rows
+        if r.step != 1:
+            raise ValueError("rows as a slice / range must have step 1 (a dense range); pass an index array otherwise")
+        row0, n_rows = (r.start, len(r)) if len(r) else (0, 0)
+    else:
+        row_idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n_rows = len(row_idx)
+    if ncols > KIN_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_KIN_MAX_ACCESSIONS)" % (ncols, KIN_MAX_ACCESSIONS))
+    ninfo, same, diff = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(3))
+    check(ctx.lib.snpm_panel_kinship_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(ninfo), ptr(same), ptr(diff)), ctx.h)
+    return ninfo, same, diff
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the
