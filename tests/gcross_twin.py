@@ -75,7 +75,10 @@ def cross_calls(codes, p1, p2, win_off, lr_thres, n_marker_thres=5):
     return geno, cnt, lr_next
 
 
+KNIFE_EDGE_WIDTH = 1e-9             # relative; tests/test_gpu_gcross_table.py measures what the device and numpy need of it
+
+
 def knife_edge_cells(lr_next, lr_thres):
     """cells whose lr_next lies within 1e-9 relative of the threshold: a last-bit difference of two log implementations could flip them"""
     with np.errstate(invalid="ignore"):
-        return int(np.count_nonzero(np.abs(lr_next - lr_thres) <= 1e-9 * lr_thres))
+        return int(np.count_nonzero(np.abs(lr_next - lr_thres) <= KNIFE_EDGE_WIDTH * lr_thres))

@@ -1,6 +1,7 @@
 """genotype_cross on the device: ``snpm_cross_calls`` / ``k_gcross`` against the reference's goldens and the numpy twin
 (tests/gcross_twin.py), whole files through ``GenotypeCross`` and the command line on int8 and packed panels, and random codes at
-the shapes where the kernel's decomposition (4 samples per lane, 256 per tile, rows split over 4 waves) could break."""
+the shapes where the kernel's decomposition (4 samples per lane, 256 per tile, rows split over 4 waves) could break.
+The decision rule itself is pinned over every count triple in tests/test_gpu_gcross_table.py: extend that table, not the random codes, for it."""
 import numpy as np
 import pytest
 
