@@ -429,8 +429,8 @@ int snpm_debug_stream_read(snpm_panel *panel, int64_t *bytes_read);
 int snpm_profile_enable(snpm_ctx *ctx, int on);
 int snpm_profile_reset(snpm_ctx *ctx);
 /* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t" (transpose of
-   snpm_pair_counts), "pairs_c" (its count), "kin_planes" / "kin_count" (the two kernels of snpm_panel_kinship_counts).
-   Synchronises the stream. */
+   snpm_pair_counts), "pairs_c" (its count), "kin_planes" / "kin_count" (the two kernels of snpm_panel_kinship_counts),
+   "site_counts" (the kernel of snpm_panel_site_counts, one launch per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -516,6 +516,32 @@ int snpm_pair_counts(snpm_ctx *ctx, const uint8_t *ids, int64_t n, int n_samples
 #define SNPM_KIN_MAX_ACCESSIONS 11552
 int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                               int32_t *ninfo, int32_t *same, int32_t *diff);
+
+/* ---------------------------------------------------------------- site statistics */
+/* Genotype.get_af_snps / calculate_af_snp_mat / _polarize_snps (core/snp_genotype.py:119-175, :360-376, :385-394 of the
+   reference: a Python loop over 1000-row chunks that gathers the panel again for every subpopulation) on the RESIDENT panel (int8
+   or packed), as one call that reads every selected row once for all groups.  Host pointers in and out.
+     cols, grp_off    CSR lists of accession columns: group g = cols[grp_off[g] .. grp_off[g + 1]), grp_off [n_groups + 1] starts at
+                      0 and does not decrease; a group may be empty, groups may overlap, a column may be listed ONCE per group
+                      (engine.site_counts splits a list with repeats into layers).  cols == NULL and grp_off == NULL with
+                      n_groups == 1: one group of all accessions
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows) (row0 is ignored
+                      when row_idx is given)
+     counts [n_groups][n_rows][4]   per group and row: c0, c1, c2 = members with canonical code 0 (ref), 1 (alt), 2 (het); ninfo =
+                      members whose call is not missing.  An int8 panel's "other" code 3 is informative and in none of c0..c2
+   The row axis is processed in slabs whose counts fit a workspace budget (256 MiB; SNPM_SITE_WS_MB, read by snpm_init):
+   slab_rows = max(64, floor(budget / (16 * n_groups)) rounded down to a multiple of 64), one launch per slab.
+   Limits: n_groups <= SNPM_SITE_MAX_GROUPS (the membership words of a launch are held in the 64 KiB of LDS of a block), panels
+   of at most 16384 accessions (eight 32-column words per lane of a wave).
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size,
+   n_groups within the limit, grp_off starts at 0 and does not decrease, non-NULL counts when there is work -- these before the
+   panel handle is looked at, the message of a NULL panel is in snpm_last_error(NULL) -- then every column inside the panel, no
+   column twice in one group, every row inside the panel.  n_groups == 0 or n_rows == 0 returns without a launch and writes
+   nothing; a call whose groups are all empty writes zeros without a launch.  Uploads into the panel that are still in flight
+   are waited for on the device. */
+#define SNPM_SITE_MAX_GROUPS 32
+int snpm_panel_site_counts(snpm_panel *panel, const int32_t *cols, const int64_t *grp_off, int64_t n_groups, const int64_t *row_idx,
+                           int64_t row0, int64_t n_rows, int32_t *counts);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

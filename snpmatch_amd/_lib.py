@@ -51,6 +51,7 @@ SYMBOLS = [
     "snpm_cross_hmm", "snpm_vcf_parse_calls_dp", "snpm_vcf_fill_calls_dp",
     "snpm_pair_counts",
     "snpm_panel_kinship_counts",
+    "snpm_panel_site_counts",
 ]
 
 _lib = None
@@ -243,6 +244,7 @@ def load():
     lib.snpm_cross_hmm.argtypes = [p, p, p, i64, ci, i64, p, p, ci, p, p, p, ci, p, p]
     lib.snpm_pair_counts.argtypes = [p, p, i64, ci, i64, p, ci, p, p]
     lib.snpm_panel_kinship_counts.argtypes = [p, p, i64, p, i64, i64, p, p, p]
+    lib.snpm_panel_site_counts.argtypes = [p, p, p, i64, p, i64, i64, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]
     lib.snpm_profile_enable.argtypes = [p, ci]
     lib.snpm_profile_reset.argtypes = [p]

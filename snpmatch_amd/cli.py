@@ -6,7 +6,8 @@ mode with the parents named as two accessions of the database (``-p 6091x6191``)
 ``--hmm`` flag is the subcommand ``genotype_cross_hmm``.  ``--hmm`` itself and ``-q / --father`` are refused with a message
 (core/genotype_cross.py says why).  ``pairsnp`` compares two sample files as the reference does; ``pairsnp-batch`` compares every
 pair of a cohort in one device call.  ``kinship`` (not in the reference as a command) counts the relatedness of every pair of
-accessions of the database on the device and lists the near-identical ones.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+accessions of the database on the device and lists the near-identical ones; ``sitestats`` (not in the reference as a command
+either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
 path.
 """
 import argparse
@@ -99,6 +100,15 @@ def snpmatch_kinship(args):
     if args['accFile']:
         check_file(args['accFile'])
     kinship.potatoKinship(args)
+
+
+def snpmatch_sitestats(args):
+    from .core import sitestats
+    check_file(args['hdf5File'])
+    for key in ('accFile', 'popFile'):
+        if args[key]:
+            check_file(args[key])
+    sitestats.potatoSiteStats(args)
 
 
 def makedb_native(args):
@@ -214,6 +224,22 @@ def get_options(description, version_message):
     kin.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     kin.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.kinship.npz and <prefix>.duplicates.tsv")
     kin.set_defaults(func=snpmatch_kinship)
+
+    # not in the reference as a command (its Genotype.get_af_snps is a method): allele counts and frequencies of every DB row per population
+    site = sub.add_parser('sitestats', help="allele counts, frequencies and missingness of every SNP of the database, per population")
+    site.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    site.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    site.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line: one population of these (default: all accessions)")
+    site.add_argument("--pops", dest="popFile", default=None, help="text file of two columns, accession and population (# lines are skipped): statistics per population")
+    site.add_argument("--bed", dest="bed", default=None, help="only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
+    site.add_argument("--min_informative", dest="min_informative", default=0, type=int,
+                      help="frequencies are nan where no more than this many accessions of the population carry a call (default 0)")
+    site.add_argument("--min_maf", dest="min_maf", default=None, type=float, help="write <prefix>.sites.tsv: rows whose maf is at least this in every population")
+    site.add_argument("--max_missing", dest="max_missing", default=None, type=float,
+                      help="write <prefix>.sites.tsv: rows whose share of accessions without a call is at most this in every population")
+    site.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    site.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.sitestats.npz, <prefix>.sitestats.json and, with a threshold, <prefix>.sites.tsv")
+    site.set_defaults(func=snpmatch_sitestats)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -428,6 +428,62 @@ class Genotype(object):
         ninfo, same, diff = self.kinship_counts(filter_acc_ix, filter_snp_ix)
         return kinship_from_counts(ninfo, same, diff)
 
+    # ------------------------------------------------------------------ site statistics
+    def site_counts(self, filter_acc_ix=None, filter_snps_ix=None):
+        """int32 [G, n, 4] -- c0, c1, c2 (listed accessions with code 0 / 1 / 2) and ninfo (listed accessions with a call) of every
+        listed DB row, counted on the resident panel in one pass (``engine.site_counts``).  ``filter_acc_ix``: None (all accessions,
+        G = 1), an index array (G = 1; a repeat counts as listed) or a dict name -> index array (G = len(dict), in the dict's
+        order).  ``filter_snps_ix``: None = all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        panel = self.panel()
+        if getattr(self, "_shard", None) is not None or not isinstance(panel, engine.Panel):
+            raise TypeError("site statistics need every accession column of the DB on one device: this DB is %s.  Run it in one "
+                            "process on one GPU with a DB that fits it (SNPMATCH_GPUS unset or one device, no torch.distributed launcher)"
+                            % ("spread over several GPUs by accession" if isinstance(panel, engine.GroupPanel) or
+                               getattr(self, "_shard", None) is not None else "streamed through the device in row slabs"))
+        rows = None
+        if filter_snps_ix is not None:
+            rows = np.asarray(filter_snps_ix, dtype=np.int64).reshape(-1)
+            if len(rows) and rows[0] >= 0 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))):
+                rows = range(int(rows[0]), int(rows[0]) + len(rows))
+        if isinstance(filter_acc_ix, dict):
+            for name, ix in filter_acc_ix.items():
+                assert type(ix) is np.ndarray, "provide numpy arrays in a dictionary when giving subpopulations (%r)" % (name,)
+            groups = [filter_acc_ix[name] for name in filter_acc_ix]
+        else:
+            groups = None if filter_acc_ix is None else [np.asarray(filter_acc_ix).reshape(-1)]
+        return engine.site_counts(panel, groups, rows)
+
+    def get_af_snps(self, no_accs_missing_info, return_nind=False, filter_snps_ix=None, filter_acc_ix=None, polarize_geno=1, return_maf=True):
+        """Allele frequency of the listed DB rows among the listed accessions (core/snp_genotype.py:119-175): fp64
+        ``(2 * #polarize_geno + #het) / (2 * #informative)``, ``nan`` where no more than ``no_accs_missing_info`` listed
+        accessions carry a call; with ``return_maf`` the smaller of it and its complement.  ``return_nind``: also the number of
+        informative accessions per row (int64).  ``filter_acc_ix`` as a dict name -> index array gives dicts name -> fp64 array for
+        both (the reference appends its counts to a float array there).  The reference walks 1000-row chunks and gathers the panel
+        once per subpopulation; here every listed row is read once on the device for all of them and the division is made once
+        per row from the same two integers.  One place where its semantics are the panel's and not numpy's: a call is missing
+        when it is negative (the reference tests ``== -1``; a panel stores every missing call as -1)."""
+        counts = self.site_counts(filter_acc_ix, filter_snps_ix)
+        if isinstance(filter_acc_ix, dict):
+            maf = {name: af_from_counts(counts[k], no_accs_missing_info, polarize_geno, return_maf) for k, name in enumerate(filter_acc_ix)}
+            nind = {name: counts[k, :, 3].astype(np.float64) for k, name in enumerate(filter_acc_ix)}
+        else:
+            maf = af_from_counts(counts[0], no_accs_missing_info, polarize_geno, return_maf)
+            nind = counts[0, :, 3].astype(np.int64)
+        return (maf, nind) if return_nind else maf
+
+    def polarize_mask(self, filter_acc_ix=None, filter_snps_ix=None, polarize_geno=1):
+        """bool [n]: the listed DB rows that ``_polarize_snps`` of the reference would flip when given the listed accessions --
+        those where more than half of the LISTED accessions (a repeat counts as listed, missing calls count in the half) carry
+        ``polarize_geno`` -- from the device counts."""
+        if polarize_geno not in (0, 1, 2):
+            raise ValueError("polarize_geno must be 0, 1 or 2, got %r" % (polarize_geno,))
+        if isinstance(filter_acc_ix, dict):
+            raise TypeError("polarize_mask takes one accession list (or None), not a dict of subpopulations")
+        n_listed = len(self.accessions) if filter_acc_ix is None else np.asarray(filter_acc_ix).size
+        counts = self.site_counts(filter_acc_ix, filter_snps_ix)
+        return counts[0, :, int(polarize_geno)] > float(n_listed) / 2
+
     # ------------------------------------------------------------------ --refine support
     def identify_segregating_snps(self, accs_ix):
         """DB rows where the given accessions do not all carry the same informative call
@@ -481,6 +537,50 @@ def calc_kinship_mat(snp, return_counts=False):
         return score, informative
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.divide(score, informative)
+
+
+def af_from_counts(counts, min_informative=0, polarize_geno=1, return_maf=True):
+    """Allele frequency from site counts [..., 4] (c0, c1, c2, ninfo): fp64 ``(2 * c[polarize_geno] + c2) / (2 * ninfo)`` -- one
+    correctly rounded division of two exact integers --, ``nan`` where ``ninfo <= min_informative``; ``return_maf``: the smaller
+    of it and ``1 - it``.  (``polarize_geno=2`` counts a het three times, as the reference's formula does.)"""
+    if polarize_geno not in (0, 1, 2):
+        raise ValueError("polarize_geno must be 0, 1 or 2, got %r" % (polarize_geno,))
+    c = np.asarray(counts).astype(np.int64)
+    ninfo = c[..., 3]
+    num_alt = 2 * c[..., int(polarize_geno)] + c[..., 2]
+    af = np.full(ninfo.shape, np.nan, dtype=np.float64)
+    ok = ninfo > min_informative
+    with np.errstate(divide="ignore", invalid="ignore"):
+        af[ok] = num_alt[ok].astype(np.float64) / (2 * ninfo[ok])
+    return np.minimum(af, 1 - af) if return_maf else af
+
+
+def calculate_af_snp_mat(snp_mat, min_informative=0, polarize_geno=1, return_maf=True):
+    """Allele frequency of the rows of a small SNP matrix [n_snp, n_acc] on the host, with the semantics of the reference's function
+    of this name (core/snp_genotype.py:360-376): a call other than -1 is informative; returns ``(maf fp64 [n_snp], num_alleles
+    int64 [n_snp])``, ``maf`` being ``(2 * #(== polarize_geno) + #(== 2)) / (2 * num_alleles)``, ``nan`` where ``num_alleles <=
+    min_informative``, folded to ``min(af, 1 - af)`` with ``return_maf``."""
+    calls = np.asarray(snp_mat)
+    num_alleles = (calls.shape[1] - np.count_nonzero(calls == -1, axis=1)).astype(np.int64)
+    num_alt = 2 * np.count_nonzero(calls == polarize_geno, axis=1).astype(np.int64) + np.count_nonzero(calls == 2, axis=1)
+    af = np.full(calls.shape[0], np.nan, dtype=np.float64)
+    ok = num_alleles > min_informative
+    with np.errstate(divide="ignore", invalid="ignore"):
+        af[ok] = num_alt[ok].astype(np.float64) / (2 * num_alleles[ok])
+    return (np.minimum(af, 1 - af) if return_maf else af), num_alleles
+
+
+def _polarize_snps(snps, polarize_geno=1, genotypes=[0, 1]):
+    """A copy of a small SNP matrix [n_snp, n_acc] in which the two homozygous codes are exchanged on every row where more than
+    half of the columns carry ``polarize_geno`` (core/snp_genotype.py:385-394).  As there, the exchange goes through the value 3:
+    a call that already is 3 on such a row comes out as ``genotypes[0]``."""
+    assert len(genotypes) == 2, "assuming it is biallelic"
+    first, second = genotypes
+    out = np.array(snps)
+    flip = np.count_nonzero(out == polarize_geno, axis=1) > float(out.shape[1]) / 2
+    rows = out[flip]
+    out[flip] = np.where(rows == first, second, np.where((rows == second) | (rows == 3), first, rows)).astype(out.dtype)
+    return out
 
 
 def _bare_chr_id(name):

@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts"};
 
 struct Buf {
     void *p = nullptr;
@@ -58,6 +58,8 @@ struct Buf {
     X(ws_pr_ids) X(ws_pr_planes) X(ws_pr_chunks) X(ws_pr_out)                                                                     \
     /* snpm_panel_kinship_counts (snpm_api_kin.hpp): bit-planes [3][cols_pad][W] of a slab; column list; row list; ninfo | same | diff */ \
     X(ws_kin_planes) X(ws_kin_cols) X(ws_kin_rows) X(ws_kin_out)                                                                  \
+    /* snpm_panel_site_counts (snpm_api_site.hpp): membership bitmasks [groups][words]; row list of a slab; counts [groups][slab rows][4] */ \
+    X(ws_site_member) X(ws_site_rows) X(ws_site_out)                                                                              \
     X(ws_once) X(ws_once_table)     /* snpm_genotype_once: its packed results (unfused form); the weight table of its coded form */ \
     X(ws_once_state)                /* {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls */             \
     /* segmented / batched scoring */                                                                                             \
@@ -100,6 +102,7 @@ struct snpm_ctx {
     size_t shared_ws_bytes = size_t(2) << 30;   // SNPM_SHARED_WS_MB: digit matrix per pass over groups of samples
     int shared_force_tiles = 0;         // SNPM_SHARED_TILES: row tiles of k_sh_mfma (tests, experiments)
     size_t kin_ws_bytes = size_t(512) << 20;    // SNPM_KIN_WS_MB: bit-planes of one row slab of snpm_panel_kinship_counts
+    size_t site_ws_bytes = size_t(256) << 20;   // SNPM_SITE_WS_MB: counts of one row slab of snpm_panel_site_counts
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -485,6 +488,7 @@ try {
     if (const char *s = getenv("SNPM_SHARED_WS_MB")) ctx->shared_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_SHARED_TILES")) ctx->shared_force_tiles = std::max(0, atoi(s));
     if (const char *s = getenv("SNPM_KIN_WS_MB")) ctx->kin_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_SITE_WS_MB")) ctx->site_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -628,6 +632,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_pairs.hpp"
 
 #include "snpm_api_kin.hpp"
+
+#include "snpm_api_site.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

@@ -768,6 +768,76 @@ def kinship_counts(panel, cols=None, rows=None):
     return ninfo, same, diff
 
 
+SITE_MAX_GROUPS = 32           # SNPM_SITE_MAX_GROUPS: groups of one ``snpm_panel_site_counts`` call
+
+
+def _site_layers(cols):
+    """A column list as layers of DISTINCT columns: layer j holds the columns listed more than j times (ascending).  A list without
+    repeats is one layer; an empty list is one empty layer."""
+    cols = np.asarray(cols).reshape(-1)
+    if cols.dtype.kind not in "iu" and len(cols):
+        raise TypeError("accession indices must be integers, got %s" % cols.dtype)
+    uniq, times = np.unique(cols.astype(np.int64), return_counts=True)
+    if len(uniq) and (uniq[0] < -2 ** 31 or uniq[-1] >= 2 ** 31):
+        raise AssertionError("accession index outside the panel")
+    return [uniq[times > j].astype(np.int32) for j in range(int(times.max()) if len(times) else 1)]
+
+
+def _site_counts_call(panel, col_lists, row_idx, row0, n_rows):
+    """one ``snpm_panel_site_counts`` call: ``col_lists`` is None (one group of all accessions) or at most SITE_MAX_GROUPS lists of
+    distinct columns.  int32 [groups, n_rows, 4]."""
+    n_groups = 1 if col_lists is None else len(col_lists)
+    out = np.empty((n_groups, n_rows, 4), dtype=np.int32)
+    cols = off = None
+    if col_lists is not None:
+        off = np.zeros(n_groups + 1, dtype=np.int64)
+        np.cumsum([len(c) for c in col_lists], out=off[1:])
+        cols = np.ascontiguousarray(np.concatenate(col_lists) if col_lists else np.zeros(0), dtype=np.int32)
+    check(panel.ctx.lib.snpm_panel_site_counts(panel.h, ptr(cols), ptr(off), n_groups, ptr(row_idx), row0, n_rows, ptr(out)), panel.ctx.h)
+    return out
+
+
+def site_counts(panel, groups=None, rows=None):
+    """Allele counts of every selected panel row per group of accession columns, one streaming pass over the resident panel for
+    up to SITE_MAX_GROUPS groups (``snpm_panel_site_counts``).  ``groups``: None (one group of all accessions), one index array
+    (one group) or a list of index arrays; groups may overlap and may be empty, and a column that a group lists k times counts k
+    times, as numpy fancy indexing would (the device takes a column once per group: such a group travels as k layers of distinct
+    columns, layer j = the columns listed more than j times, and the layers' counts are added here).  ``rows``: panel rows as an
+    index array, any order, repeats allowed, or a ``slice`` / ``range`` of step 1 (a dense range), or None (all rows).
+    Returns int32 [G, n_rows, 4]: per group and row c0, c1, c2 (members with code 0 / 1 / 2) and ninfo (members with a call; an
+    int8 panel's code 3 is informative and in none of c0..c2).  More groups (layers) than SITE_MAX_GROUPS take several calls.
+    Only a panel whose columns all live on one device can be asked: group (accession-sharded) and streamed panels are refused."""
+    if not isinstance(panel, Panel):
+        raise TypeError("site_counts needs every accession column on one device: a %s is %s, load the DB as one resident "
+                        "panel (int8 or packed) on one GPU" % (type(panel).__name__, "spread over several GPUs by accession"
+                                                               if isinstance(panel, GroupPanel) else "not a resident panel"))
+    row0, row_idx = 0, None
+    if rows is None:
+        n_rows = panel.n_snp
+    elif isinstance(rows, (slice, range)):
+        r = range(*rows.indices(panel.n_snp)) if isinstance(rows, slice) else rows
+        if r.step != 1:
+            raise ValueError("rows as a slice / range must have step 1 (a dense range); pass an index array otherwise")
+        row0, n_rows = (r.start, len(r)) if len(r) else (0, 0)
+    else:
+        row_idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n_rows = len(row_idx)
+    if groups is None:
+        return _site_counts_call(panel, None, row_idx, row0, n_rows)
+    if isinstance(groups, np.ndarray) or (len(groups) and np.isscalar(groups[0])):
+        groups = [groups]
+    layers, owner = [], []
+    for g, cols in enumerate(groups):
+        for layer in _site_layers(cols):
+            layers.append(layer)
+            owner.append(g)
+    out = np.zeros((len(groups), n_rows, 4), dtype=np.int32)
+    for at in range(0, len(layers), SITE_MAX_GROUPS):
+        part = _site_counts_call(panel, layers[at:at + SITE_MAX_GROUPS], row_idx, row0, n_rows)
+        np.add.at(out, owner[at:at + SITE_MAX_GROUPS], part)
+    return out
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the
