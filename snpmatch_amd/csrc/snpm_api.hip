@@ -56,10 +56,13 @@ struct Buf {
     X(ws_gh_codes) X(ws_gh_depth) X(ws_gh_bp) X(ws_gh_state) X(ws_gh_pair) X(ws_gh_off) X(ws_gh_tab) X(ws_gh_omega)               \
     /* snpm_pair_counts (snpm_api_pairs.hpp): ids [n, pitch]; sample-major planes [pitch, n_pad]; chunk table; common | match */  \
     X(ws_pr_ids) X(ws_pr_planes) X(ws_pr_chunks) X(ws_pr_out)                                                                     \
-    /* snpm_panel_kinship_counts (snpm_api_kin.hpp): bit-planes [3][cols_pad][W] of a slab; column list; row list; ninfo | same | diff */ \
-    X(ws_kin_planes) X(ws_kin_cols) X(ws_kin_rows) X(ws_kin_out)                                                                  \
-    /* snpm_panel_site_counts (snpm_api_site.hpp): membership bitmasks [groups][words]; row list of a slab; counts [groups][slab rows][4] */ \
-    X(ws_site_member) X(ws_site_rows) X(ws_site_out)                                                                              \
+    /* snpm_panel_kinship_counts (snpm_api_kin.hpp): bit-planes [3][cols_pad][W] of a slab; column list; ninfo | same | diff */ \
+    X(ws_kin_planes) X(ws_kin_cols) X(ws_kin_out)                                                                                 \
+    /* snpm_panel_site_counts (snpm_api_site.hpp): membership bitmasks [groups][words]; counts [groups][slab rows][4] */ \
+    X(ws_site_member) X(ws_site_out)                                                                                              \
+    /* the row list of ONE slab of either panel scan (snpm_api_rows.hpp).  One buffer for both: a context has one stream, and   */ \
+    /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
+    X(ws_rows)                                                                                                                    \
     X(ws_once) X(ws_once_table)     /* snpm_genotype_once: its packed results (unfused form); the weight table of its coded form */ \
     X(ws_once_state)                /* {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls */             \
     /* segmented / batched scoring */                                                                                             \
@@ -416,6 +419,8 @@ int wait_upload(snpm_panel *p)
 #include "snpm_api_seg.hpp"
 
 #include "snpm_api_shared.hpp"
+
+#include "snpm_api_rows.hpp"
 }  // namespace
 
 #include "snpm_loader.hpp"

@@ -11,15 +11,8 @@ int snpm_cross_calls(snpm_ctx *ctx, const uint8_t *gt_codes, int64_t n, int n_sa
     CHECK_ARG(ctx, ld >= n_samples, "ld smaller than n_samples");
     CHECK_ARG(ctx, (int64_t)n_samples <= (int64_t)65535 * GC_TILE, "too many samples for one call");
     CHECK_ARG(ctx, lr_thres == lr_thres, "lr_thres is NaN");
-    if (n_win > 0) {
-        CHECK_ARG(ctx, win_off != nullptr, "win_off is NULL");
-        CHECK_ARG(ctx, win_off[0] == 0, "win_off must start at 0");
-        for (int w = 0; w < n_win; ++w) {
-            CHECK_ARG(ctx, win_off[w + 1] >= win_off[w], "win_off must not decrease");
-            CHECK_ARG(ctx, win_off[w + 1] - win_off[w] <= INT32_MAX, "a window holds more than 2^31 - 1 markers");
-        }
-        CHECK_ARG(ctx, win_off[n_win] == n, "win_off must end at n");
-    }
+    if (n_win > 0)
+        if (int bad = check_offsets(ctx, "win_off", win_off, n_win, n, INT32_MAX, "a window holds more than 2^31 - 1 markers")) return bad;
     if (n > 0) {
         CHECK_ARG(ctx, p1 != nullptr && p2 != nullptr, "p1 / p2 is NULL");
         for (int64_t r = 0; r < n; ++r) {
@@ -31,7 +24,7 @@ int snpm_cross_calls(snpm_ctx *ctx, const uint8_t *gt_codes, int64_t n, int n_sa
             for (int64_t r = 0; r < n; ++r) {
                 const uint8_t *row = gt_codes + r * ld;
                 bool ok = true;
-                for (int s = 0; s < n_samples; ++s) ok &= (row[s] & 7u) <= 4u && (row[s] & 0xF0u) == 0;
+                for (int s = 0; s < n_samples; ++s) ok &= gt_code_defined(row[s]);
                 CHECK_ARG(ctx, ok, "a genotype code outside the defined ones (0xFF: a genotype without a separator)");
             }
         }

@@ -12,10 +12,7 @@ int snpm_cross_hmm(snpm_ctx *ctx, const uint8_t *gt_codes, const uint16_t *depth
     CHECK_ARG(ctx, (int64_t)n_samples <= (int64_t)65535 * WAVE, "too many samples for one call");
     CHECK_ARG(ctx, n_depth <= 65536, "n_depth above 65536: a depth rank is 16 bits wide");
     if (n_chain > 0) {
-        CHECK_ARG(ctx, chain_off != nullptr, "chain_off is NULL");
-        CHECK_ARG(ctx, chain_off[0] == 0, "chain_off must start at 0");
-        for (int c = 0; c < n_chain; ++c) CHECK_ARG(ctx, chain_off[c + 1] >= chain_off[c], "chain_off must not decrease");
-        CHECK_ARG(ctx, chain_off[n_chain] == n, "chain_off must end at n");
+        if (int bad = check_offsets(ctx, "chain_off", chain_off, n_chain, n)) return bad;
         CHECK_ARG(ctx, logT != nullptr, "logT is NULL");
         for (int64_t k = 0; k < (int64_t)n_chain * 9; ++k) CHECK_ARG(ctx, logT[k] == logT[k] && logT[k] != __builtin_inf(), "NaN or +inf in logT");
     } else {
@@ -38,7 +35,7 @@ int snpm_cross_hmm(snpm_ctx *ctx, const uint8_t *gt_codes, const uint16_t *depth
                 const uint16_t *drow = depth_rank + r * ld;
                 bool ok = true, dok = true;
                 for (int s = 0; s < n_samples; ++s) {
-                    ok &= (row[s] & 7u) <= 4u && (row[s] & 0xF0u) == 0;
+                    ok &= gt_code_defined(row[s]);
                     dok &= (int)drow[s] < n_depth;
                 }
                 CHECK_ARG(ctx, ok, "a genotype code outside the defined ones (0xFF: a genotype without a separator)");

@@ -19,11 +19,7 @@ int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t nc
     } else {
         CHECK_ARG(ctx, ncols == 0 || ncols == p->n_acc, "cols is NULL (all accessions): ncols must be the panel's accession count");
     }
-    if (row_idx) {
-        for (int64_t r = 0; r < n_rows; ++r) CHECK_ARG(ctx, row_idx[r] >= 0 && row_idx[r] < p->n_snp, "row index outside the panel");
-    } else {
-        CHECK_ARG(ctx, row0 >= 0 && row0 <= p->n_snp && n_rows <= p->n_snp - row0, "row range outside the panel");
-    }
+    if (int bad = check_rows(ctx, p, row_idx, row0, n_rows)) return bad;
     if (ncols == 0) return SNPM_OK;                                  // nothing to write, nothing launched
     const size_t cells = (size_t)ncols * (size_t)ncols;
     if (n_rows == 0) {                                               // zero counts, nothing launched
@@ -37,35 +33,25 @@ int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t nc
     if (rc) return rc;
     const int64_t cols_pad = (ncols + KN_PL_COLS - 1) / KN_PL_COLS * KN_PL_COLS;
     const int n_tiles = (int)((ncols + KN_TILE - 1) / KN_TILE);
-    // slabs of the row axis: whole LDS steps (1024 rows) of planes inside the workspace budget -- whole chunks where the budget holds
-    // one -- and at most 65535 chunks (grid.y)
-    const int64_t step_rows = (int64_t)KN_STEP_WORDS * 64, steps_per_chunk = KN_CHUNK_WORDS / KN_STEP_WORDS;
-    const int64_t step_bytes = 3 * cols_pad * KN_STEP_WORDS * 8;
-    int64_t slab_steps = std::max<int64_t>(1, (int64_t)(ctx->kin_ws_bytes / (size_t)step_bytes));
-    if (slab_steps >= steps_per_chunk) slab_steps = slab_steps / steps_per_chunk * steps_per_chunk;
-    slab_steps = std::min<int64_t>(slab_steps, 65535 * steps_per_chunk);
-    slab_steps = std::min<int64_t>(slab_steps, (n_rows + step_rows - 1) / step_rows);
-    const int64_t slab_rows = slab_steps * step_rows;
-    if ((rc = ensure(ctx, ctx->ws_kin_planes, (size_t)slab_steps * (size_t)step_bytes))) return rc;
+    // slabs of the row axis: whole LDS steps of planes inside the workspace budget (kin_slab_steps of snpm_k_kin.hpp)
+    const int64_t slab_steps = kin_slab_steps(ctx->kin_ws_bytes, cols_pad, n_rows), slab_rows = slab_steps * KN_STEP_ROWS;
+    if ((rc = ensure(ctx, ctx->ws_kin_planes, (size_t)slab_steps * (size_t)kin_step_bytes(cols_pad)))) return rc;
     if ((rc = ensure(ctx, ctx->ws_kin_out, 3 * cells * sizeof(int32_t)))) return rc;
     if (cols && (rc = ensure(ctx, ctx->ws_kin_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if (row_idx && (rc = ensure(ctx, ctx->ws_kin_rows, (size_t)std::min(slab_rows, n_rows) * sizeof(int64_t)))) return rc;   // the rows of ONE slab
+    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
     const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_kin_cols.p : nullptr;
-    const int64_t *d_rows = row_idx ? (const int64_t *)ctx->ws_kin_rows.p : nullptr;
     int32_t *d_ninfo = (int32_t *)ctx->ws_kin_out.p, *d_same = d_ninfo + cells, *d_diff = d_same + cells;
     unsigned long long *d_planes = (unsigned long long *)ctx->ws_kin_planes.p;
     if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_kin_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_ninfo, 0, 3 * cells * sizeof(int32_t), ctx->stream));
-    for (int64_t s0 = 0; s0 < n_rows; s0 += slab_rows) {             // the results accumulate on the device across slabs
-        const int64_t n_valid = std::min(slab_rows, n_rows - s0);
-        const int64_t W = (n_valid + step_rows - 1) / step_rows * KN_STEP_WORDS;      // words per plane row of this slab
-        // a row list travels slab by slab (stream order: the previous slab's plane kernel has read its part before this copy lands)
-        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_kin_rows.p, row_idx + s0, (size_t)n_valid * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    // the results accumulate on the device across slabs
+    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t, int64_t n_valid) {
+        const int64_t W = (n_valid + KN_STEP_ROWS - 1) / KN_STEP_ROWS * KN_STEP_WORDS;      // words per plane row of this slab
         {
             ProfScope ps(ctx, PK_KIN_P);
             const dim3 grid((unsigned)W, (unsigned)(cols_pad / KN_PL_COLS));
             hipLaunchKernelGGL(k_kin_planes, grid, dim3(KN_THREADS), 0, ctx->stream, (const int8_t *)p->d, p->kpitch, p->desc, d_rows,
-                               row_idx ? (int64_t)0 : row0 + s0, n_valid, d_cols, (int)ncols, d_planes, cols_pad, W);
+                               first, n_valid, d_cols, (int)ncols, d_planes, cols_pad, W);
             HIPCHK(ctx, hipGetLastError());
         }
         {
@@ -75,7 +61,9 @@ int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t nc
                                n_tiles, d_ninfo, d_same, d_diff);
             HIPCHK(ctx, hipGetLastError());
         }
-    }
+        return (int)SNPM_OK;
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ninfo, d_ninfo, cells * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(same, d_same, cells * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(diff, d_diff, cells * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));

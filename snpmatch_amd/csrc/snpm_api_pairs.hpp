@@ -11,13 +11,7 @@ int snpm_pair_counts(snpm_ctx *ctx, const uint8_t *ids, int64_t n, int n_samples
     CHECK_ARG(ctx, n_samples <= SNPM_PAIR_MAX_SAMPLES, "too many samples for one call (SNPM_PAIR_MAX_SAMPLES)");
     CHECK_ARG(ctx, (int64_t)n_seg * n_samples * n_samples <= SNPM_PAIR_MAX_CELLS, "n_seg * n_samples^2 above SNPM_PAIR_MAX_CELLS: split the segments over several calls");
     if (n_seg > 0) {
-        CHECK_ARG(ctx, seg_off != nullptr, "seg_off is NULL");
-        CHECK_ARG(ctx, seg_off[0] == 0, "seg_off must start at 0");
-        for (int s = 0; s < n_seg; ++s) {
-            CHECK_ARG(ctx, seg_off[s + 1] >= seg_off[s], "seg_off must not decrease");
-            CHECK_ARG(ctx, seg_off[s + 1] - seg_off[s] <= INT32_MAX, "a segment holds 2^31 records or more: its counts would not fit int32");
-        }
-        CHECK_ARG(ctx, seg_off[n_seg] == n, "seg_off must end at n");
+        if (int bad = check_offsets(ctx, "seg_off", seg_off, n_seg, n, INT32_MAX, "a segment holds 2^31 records or more: its counts would not fit int32")) return bad;
     } else {
         CHECK_ARG(ctx, n == 0, "seg_off must end at n");
     }

@@ -6,9 +6,8 @@
 // index lying inside the panel and on membership bits at or beyond n_acc being zero.
 //
 // Slabs: the row axis is cut so that the counts of a slab, 16 bytes per (group, row), fit the workspace budget (SNPM_SITE_WS_MB):
-//   slab_rows = max(64, floor(budget / (16 * n_groups)) rounded down to a multiple of 64)
-// One launch per slab; its counts are copied to the caller's array before the next slab's launch overwrites the workspace (stream
-// order); a row list travels slab by slab.
+// site_slab_rows of snpm_k_site.hpp.  One launch per slab (for_each_row_slab); its counts are copied to the caller's array before
+// the next slab's launch overwrites the workspace (stream order); a row list travels slab by slab.
 int snpm_panel_site_counts(snpm_panel *panel, const int32_t *cols, const int64_t *grp_off, int64_t n_groups, const int64_t *row_idx,
                            int64_t row0, int64_t n_rows, int32_t *counts)
 try {
@@ -17,8 +16,7 @@ try {
     CHECK_ARG(ctx, n_groups <= SNPM_SITE_MAX_GROUPS, "too many groups for one call (SNPM_SITE_MAX_GROUPS)");
     if (cols || grp_off) {
         CHECK_ARG(ctx, grp_off != nullptr, "grp_off is NULL with a column list");
-        CHECK_ARG(ctx, grp_off[0] == 0, "grp_off must start at 0");
-        for (int64_t g = 0; g < n_groups; ++g) CHECK_ARG(ctx, grp_off[g + 1] >= grp_off[g], "grp_off must not decrease");
+        if (int bad = check_offsets(ctx, "grp_off", grp_off, n_groups, -1)) return bad;      // (any end: the columns listed)
         CHECK_ARG(ctx, cols != nullptr || grp_off[n_groups] == 0, "cols is NULL but grp_off lists columns");
     } else {
         CHECK_ARG(ctx, n_groups <= 1, "cols is NULL (all accessions): n_groups must be 1");
@@ -43,11 +41,7 @@ try {
         for (int64_t c = 0; c < p->n_acc; ++c) member[(size_t)(c >> 5)] |= 1u << (c & 31);
         any_member = true;
     }
-    if (row_idx) {
-        for (int64_t r = 0; r < n_rows; ++r) CHECK_ARG(ctx, row_idx[r] >= 0 && row_idx[r] < p->n_snp, "row index outside the panel");
-    } else {
-        CHECK_ARG(ctx, row0 >= 0 && row0 <= p->n_snp && n_rows <= p->n_snp - row0, "row range outside the panel");
-    }
+    if (int bad = check_rows(ctx, p, row_idx, row0, n_rows)) return bad;
     int lg_s = 0, cpl = 0;
     CHECK_ARG(ctx, site_geometry(p->n_acc, p->packed != 0, &lg_s, &cpl), "the panel is wider than one wave's words (16384 accessions)");
     if (n_groups == 0 || n_rows == 0) return SNPM_OK;               // nothing to write, nothing launched
@@ -58,24 +52,19 @@ try {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = wait_upload(p);
     if (rc) return rc;
-    int64_t slab_rows = std::max<int64_t>(64, (int64_t)(ctx->site_ws_bytes / (size_t)(16 * n_groups)) / 64 * 64);
-    slab_rows = std::min(slab_rows, n_rows);
+    const int64_t slab_rows = site_slab_rows(ctx->site_ws_bytes, n_groups, n_rows);
     if ((rc = ensure(ctx, ctx->ws_site_out, (size_t)n_groups * (size_t)slab_rows * 16))) return rc;
     if ((rc = ensure(ctx, ctx->ws_site_member, member.size() * sizeof(uint32_t)))) return rc;
-    if (row_idx && (rc = ensure(ctx, ctx->ws_site_rows, (size_t)slab_rows * sizeof(int64_t)))) return rc;     // the rows of ONE slab
-    const int64_t *d_rows = row_idx ? (const int64_t *)ctx->ws_site_rows.p : nullptr;
+    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
     int32_t *d_out = (int32_t *)ctx->ws_site_out.p;
     HIPCHK(ctx, hipMemcpyAsync(ctx->ws_site_member.p, member.data(), member.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     const int rpw = WAVE >> lg_s, waves = SITE_THREADS / WAVE;
     const bool wide = site_wide_rows(p->d, p->kpitch, p->desc);      // every panel the library makes, except split rows with a tail below 16 bytes
-    for (int64_t s0 = 0; s0 < n_rows; s0 += slab_rows) {
-        const int64_t n_valid = std::min(slab_rows, n_rows - s0);
-        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_site_rows.p, row_idx + s0, (size_t)n_valid * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         {
             ProfScope ps(ctx, PK_SITE);
             const int64_t batches = (n_valid + rpw - 1) / rpw;
             const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((batches + waves - 1) / waves, (int64_t)ctx->n_cu * 2)));
-            const int64_t first = row_idx ? (int64_t)0 : row0 + s0;
 #define SNPM_SITE_LAUNCH(PK, WD)                                                                                                  \
     hipLaunchKernelGGL((k_site_counts<PK, WD>), grid, dim3(SITE_THREADS), 0, ctx->stream, (const int8_t *)p->d, p->kpitch, p->desc, p->n_acc, \
                        d_rows, first, n_valid, (const uint32_t *)ctx->ws_site_member.p, (int)n_groups, lg_s, cpl, d_out)
@@ -86,7 +75,9 @@ try {
         }
         for (int64_t g = 0; g < n_groups; ++g)                       // the slab's [g][n_valid][4] into the caller's [g][n_rows][4]
             HIPCHK(ctx, hipMemcpyAsync(counts + (g * n_rows + s0) * 4, d_out + g * n_valid * 4, (size_t)n_valid * 16, hipMemcpyDeviceToHost, ctx->stream));
-    }
+        return (int)SNPM_OK;
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                 // (the caller's row_idx and `member` are read until here)
     return SNPM_OK;
 } SNPM_GUARD((panel ? panel->ctx : nullptr))

@@ -1,6 +1,6 @@
 // snpm_k_kin.hpp -- panel kinship: all-pairs accession relatedness over panel rows (Genotype.kinship_given_snps / calc_kinship_mat, core/snp_genotype.py:256-289, :440-459 of the reference).
 // One of the kernel-family headers behind snpm_kernels.hpp (include that one).  It needs pk_off / WAVE of snpm_k_common.hpp only, so
-// that tests/kin_host_driver.cpp can compile this very text for the host.
+// that tests/kin_host_driver.cpp can compile this very text for the host (tests/host_kernel/).
 #pragma once
 
 namespace snpm {
@@ -39,6 +39,21 @@ constexpr int KN_PL_LD = KN_PL_COLS + 4;    // bytes per LDS row of the tile (17
 static_assert(KN_CHUNK_WORDS % KN_STEP_WORDS == 0 && KN_PL_COLS % KN_TILE == 0 && KN_PL_ROWS == WAVE, "whole steps per chunk, whole count tiles per plane tile, a ballot is a word");
 static_assert(KN_TILE * KN_TILE == 4 * KN_THREADS, "a 2 x 2 register tile of pairs per lane");
 static_assert(KN_TILE * KN_STEP_WORDS * 8 / 16 == KN_THREADS, "one 16-byte load per thread, plane and side of a step");
+
+// The host's slab plan: LDS steps (KN_STEP_ROWS rows each) of one slab of an n_rows scan whose planes [3][cols_pad][W] must fit
+// ws_bytes -- whole chunks where the budget holds one, at least one step, at most 65535 chunks (grid.y of k_kin_count) and no more
+// than the rows need.  A slab's planes take kin_slab_steps(..) * kin_step_bytes(cols_pad) bytes.
+constexpr int64_t KN_STEP_ROWS = (int64_t)KN_STEP_WORDS * 64;
+__host__ __device__ __forceinline__ int64_t kin_step_bytes(int64_t cols_pad) { return 3 * cols_pad * KN_STEP_WORDS * 8; }
+__host__ __device__ __forceinline__ int64_t kin_slab_steps(size_t ws_bytes, int64_t cols_pad, int64_t n_rows)
+{
+    const int64_t steps_per_chunk = KN_CHUNK_WORDS / KN_STEP_WORDS, need = (n_rows + KN_STEP_ROWS - 1) / KN_STEP_ROWS;
+    int64_t steps = (int64_t)(ws_bytes / (size_t)kin_step_bytes(cols_pad));
+    if (steps < 1) steps = 1;
+    if (steps >= steps_per_chunk) steps = steps / steps_per_chunk * steps_per_chunk;
+    if (steps > 65535 * steps_per_chunk) steps = 65535 * steps_per_chunk;
+    return steps < need ? steps : need;
+}
 
 // canonical code of (row, accession): 0 ref, 1 alt, 2 het, 3 other (int8 panels), 0xFF missing.  `desc` is the panel's layout
 // descriptor (snpm_k_common.hpp): 0 = int8 rows of `pitch` bytes, else 2-bit fields in whole or split rows.

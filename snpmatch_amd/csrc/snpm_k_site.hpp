@@ -1,6 +1,6 @@
 // snpm_k_site.hpp -- site statistics: per-SNP allele counts per group of accessions over panel rows (Genotype.get_af_snps / calculate_af_snp_mat / _polarize_snps, core/snp_genotype.py:119-175, :360-376, :385-394 of the reference).
 // One of the kernel-family headers behind snpm_kernels.hpp (include that one).  It needs pk_off and friends / WAVE of snpm_k_common.hpp
-// only, so that tests/site_host_driver.cpp can compile this very text for the host.
+// only, so that tests/site_host_driver.cpp can compile this very text for the host (tests/host_kernel/).
 #pragma once
 
 #ifndef SNPM_SITE_MAX_GROUPS
@@ -75,6 +75,14 @@ __host__ __device__ __forceinline__ bool site_geometry(int64_t n_acc, bool packe
     *lg_s = lg;
     *cpl = (int)((chunks + ((int64_t)1 << lg) - 1) >> lg);
     return *cpl <= most;
+}
+
+// The host's slab plan: rows of one slab of an n_rows scan whose counts, 16 bytes per (group, row), must fit ws_bytes -- a multiple
+// of 64, at least 64, and no more than n_rows.
+__host__ __device__ __forceinline__ int64_t site_slab_rows(size_t ws_bytes, int64_t n_groups, int64_t n_rows)
+{
+    const int64_t fit = (int64_t)(ws_bytes / (size_t)(16 * n_groups)) / 64 * 64, rows = fit < 64 ? 64 : fit;
+    return rows < n_rows ? rows : n_rows;
 }
 
 // the membership bits of word w of lane `sub` (of S = 1 << lg_s lanes per row) in the bit order of that lane's indicators.

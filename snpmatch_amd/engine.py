@@ -729,6 +729,27 @@ def pair_counts(ctx, ids, seg_off):
     return common, match
 
 
+def _need_resident_panel(panel, caller):
+    """the refusal of ``kinship_counts`` / ``site_counts`` for group (accession-sharded) and streamed panels"""
+    if not isinstance(panel, Panel):
+        raise TypeError("%s needs every accession column on one device: a %s is %s, load the DB as one resident "
+                        "panel (int8 or packed) on one GPU" % (caller, type(panel).__name__, "spread over several GPUs by accession"
+                                                               if isinstance(panel, GroupPanel) else "not a resident panel"))
+
+
+def _row_selection(panel, rows):
+    """``rows`` (None, a ``slice`` / ``range`` of step 1, or an index array) as the library's ``(row_idx, row0, n_rows)``"""
+    if rows is None:
+        return None, 0, panel.n_snp
+    if isinstance(rows, (slice, range)):
+        r = range(*rows.indices(panel.n_snp)) if isinstance(rows, slice) else rows
+        if r.step != 1:
+            raise ValueError("rows as a slice / range must have step 1 (a dense range); pass an index array otherwise")
+        return (None, r.start, len(r)) if len(r) else (None, 0, 0)
+    row_idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    return row_idx, 0, len(row_idx)
+
+
 KIN_MAX_ACCESSIONS = 11552     # SNPM_KIN_MAX_ACCESSIONS: columns of one ``kinship_counts`` call
 
 
@@ -740,27 +761,14 @@ def kinship_counts(panel, cols=None, rows=None):
     both are homozygous and equal, rows where both are homozygous and different.  The reference's kinship is
     ``(same - diff) / ninfo``.  Only a panel whose columns all live on one device can be asked: group (accession-sharded) and
     streamed panels are refused."""
-    if not isinstance(panel, Panel):
-        raise TypeError("kinship_counts needs every accession column on one device: a %s is %s, load the DB as one resident "
-                        "panel (int8 or packed) on one GPU" % (type(panel).__name__, "spread over several GPUs by accession"
-                                                               if isinstance(panel, GroupPanel) else "not a resident panel"))
+    _need_resident_panel(panel, "kinship_counts")
     ctx = panel.ctx
     if cols is None:
         ncols = panel.n_acc
     else:
         cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
         ncols = len(cols)
-    row0, row_idx = 0, None
-    if rows is None:
-        n_rows = panel.n_snp
-    elif isinstance(rows, (slice, range)):
-        r = range(*rows.indices(panel.n_snp)) if isinstance(rows, slice) else rows
-        if r.step != 1:
-            raise ValueError("rows as a slice / range must have step 1 (a dense range); pass an index array otherwise")
-        row0, n_rows = (r.start, len(r)) if len(r) else (0, 0)
-    else:
-        row_idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        n_rows = len(row_idx)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
     if ncols > KIN_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
         raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_KIN_MAX_ACCESSIONS)" % (ncols, KIN_MAX_ACCESSIONS))
     ninfo, same, diff = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(3))
@@ -807,21 +815,8 @@ def site_counts(panel, groups=None, rows=None):
     Returns int32 [G, n_rows, 4]: per group and row c0, c1, c2 (members with code 0 / 1 / 2) and ninfo (members with a call; an
     int8 panel's code 3 is informative and in none of c0..c2).  More groups (layers) than SITE_MAX_GROUPS take several calls.
     Only a panel whose columns all live on one device can be asked: group (accession-sharded) and streamed panels are refused."""
-    if not isinstance(panel, Panel):
-        raise TypeError("site_counts needs every accession column on one device: a %s is %s, load the DB as one resident "
-                        "panel (int8 or packed) on one GPU" % (type(panel).__name__, "spread over several GPUs by accession"
-                                                               if isinstance(panel, GroupPanel) else "not a resident panel"))
-    row0, row_idx = 0, None
-    if rows is None:
-        n_rows = panel.n_snp
-    elif isinstance(rows, (slice, range)):
-        r = range(*rows.indices(panel.n_snp)) if isinstance(rows, slice) else rows
-        if r.step != 1:
-            raise ValueError("rows as a slice / range must have step 1 (a dense range); pass an index array otherwise")
-        row0, n_rows = (r.start, len(r)) if len(r) else (0, 0)
-    else:
-        row_idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        n_rows = len(row_idx)
+    _need_resident_panel(panel, "site_counts")
+    row_idx, row0, n_rows = _row_selection(panel, rows)
     if groups is None:
         return _site_counts_call(panel, None, row_idx, row0, n_rows)
     if isinstance(groups, np.ndarray) or (len(groups) and np.isscalar(groups[0])):

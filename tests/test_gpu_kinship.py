@@ -5,6 +5,7 @@ of the count kernel (a 2 x 2 register tile of pairs per lane; the plane kernel w
 1024 rows per LDS step, 8192 rows per chunk, slabs of the row axis; and ``Genotype.kinship_given_snps`` against the reference's
 goldens."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -92,6 +93,41 @@ def test_three_slabs_with_a_ragged_last_one(layout, monkeypatch):
         order = rng.permutation(len(snps))[:2 * CHUNK + 5].astype(np.int64)           # a row list crosses slabs too
         _check(panel, snps, rows=order)
         assert small.profile_read("kin_count")[0] == 3
+        small.profile(False)
+        panel.free()
+    finally:
+        small.close()
+
+
+def _kernel_constant(name):
+    """a ``constexpr int`` of csrc/snpm_k_kin.hpp"""
+    text = open(os.path.join(os.path.dirname(os.path.abspath(engine.__file__)), "csrc", "snpm_k_kin.hpp")).read()
+    return int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
+
+
+def test_a_row_list_of_three_slabs_over_a_small_panel(monkeypatch):
+    """SNPM_KIN_WS_MB=1: 33 accessions are 64 padded columns, 24 KiB of planes per 1024-row step -- the budget holds 42 steps, cut
+    to the 40 of five whole chunks: a slab is 40960 rows.  The list is longer than the panel: 2 slabs + 65 entries, with repeats,
+    each slab's part uploaded on its own."""
+    step_words, chunk_words, pl_cols = (_kernel_constant(k) for k in ("KN_STEP_WORDS", "KN_CHUNK_WORDS", "KN_PL_COLS"))
+    cols_pad = -(-33 // pl_cols) * pl_cols
+    steps = max(1, (1 << 20) // (3 * cols_pad * step_words * 8))
+    per_chunk = chunk_words // step_words
+    if steps >= per_chunk:
+        steps = steps // per_chunk * per_chunk
+    slab_rows = min(steps, 65535 * per_chunk) * step_words * 64
+    assert chunk_words * 64 == CHUNK and slab_rows == 40960
+    monkeypatch.setenv("SNPM_KIN_WS_MB", "1")
+    small = engine.Context(0)
+    try:
+        rng = np.random.default_rng(8000)
+        snps = _calls(rng, 300, 33)
+        panel = _panel(small, snps, "packed", monkeypatch)
+        rows = rng.integers(0, 300, size=2 * slab_rows + 65).astype(np.int64)
+        small.profile(True)
+        small.profile_reset()
+        _check(panel, snps, rows=rows)
+        assert small.profile_read("kin_planes")[0] == 3 and small.profile_read("kin_count")[0] == 3
         small.profile(False)
         panel.free()
     finally:

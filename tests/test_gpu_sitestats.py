@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import kinship_twin
 import sitestats_twin
 from snpmatch_amd import engine
 from snpmatch_amd.core import snp_genotype
@@ -121,6 +122,48 @@ def test_three_slabs_with_a_ragged_last_one(layout, monkeypatch):
         panel.free()
     finally:
         small.close()
+
+
+def test_a_row_list_of_three_slabs_over_a_small_panel(monkeypatch):
+    """SNPM_SITE_WS_MB=1 and three groups: slabs of 21824 rows; the list is longer than the panel: 2 slabs + 65 entries, with
+    repeats, each slab's part uploaded on its own"""
+    monkeypatch.setenv("SNPM_SITE_WS_MB", "1")
+    small = engine.Context(0)
+    try:
+        rng = np.random.default_rng(8000)
+        slab_rows = max(64, (1 << 20) // (16 * 3) // 64 * 64)
+        assert slab_rows == 21824
+        snps = _calls(rng, 300, 130)
+        panel = _panel(small, snps, "split", monkeypatch)
+        rows = rng.integers(0, 300, size=2 * slab_rows + 65).astype(np.int64)
+        small.profile(True)
+        small.profile_reset()
+        _check(panel, snps, _groups(rng, 130, "three"), rows)
+        assert small.profile_read("site_counts")[0] == 3
+        small.profile(False)
+        panel.free()
+    finally:
+        small.close()
+
+
+def test_kinship_and_site_calls_share_the_row_buffer_of_a_context(monkeypatch):
+    """one context, one row-list workspace for both scans: site counts, kinship and site counts again, each with a row list of its
+    own (unsorted, with repeats, of different lengths), each equal to its twin"""
+    one = engine.Context(0)
+    try:
+        rng = np.random.default_rng(9000)
+        snps = _calls(rng, 300, 130, other=True)
+        panel = _panel(one, snps, "int8", monkeypatch)
+        groups = _groups(rng, 130, "three")
+        _check(panel, snps, groups, rng.integers(0, 300, size=200).astype(np.int64))
+        kin_rows = rng.integers(0, 300, size=129).astype(np.int64)
+        got = engine.kinship_counts(panel, None, kin_rows)
+        for g, w in zip(got, kinship_twin.kinship_counts(snps, None, kin_rows)):
+            assert g.dtype == np.int32 and np.array_equal(g, w)
+        _check(panel, snps, groups, rng.integers(0, 300, size=260).astype(np.int64))
+        panel.free()
+    finally:
+        one.close()
 
 
 def test_a_smaller_second_call_sees_nothing_of_the_first_and_the_refusals_that_need_a_panel(ctx, monkeypatch):

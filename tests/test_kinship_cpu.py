@@ -2,14 +2,14 @@
 goldens (counts equal, kinship equal as fp64 bits, ``nan`` where the reference has ``nan``); every refusal of
 ``snpm_panel_kinship_counts`` that needs no device; the ``kinship`` subcommand with the twin in the place of the device call; and the
 kernel source itself, compiled for the host and run by 256 real threads per block under AddressSanitizer + UBSan
-(tests/kin_host_driver.cpp, a child process)."""
+(tests/kin_host_driver.cpp on tests/host_kernel/, a child process)."""
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_kernel_util
 import kinship_twin
 from snpmatch_amd import _lib, cli, engine
 from snpmatch_amd.core import kinship, snp_genotype
@@ -214,18 +214,8 @@ def test_duplicate_pairs_needs_sites_and_sorts_ties_by_name():
 def test_kernel_source_on_the_host_under_asan_and_ubsan(tmp_path):
     """every block of k_kin_planes / k_kin_count run by 256 real threads with a barrier, exact-size heap buffers, stale planes:
     1 / 2 / 31 / 32 / 33 / 65 / 130 accessions x 0 / 1 / 63 / 64 / 65 rows in the three layouts, a chunk - 1 / exact / + 1, two
-    slabs (whole chunks and single LDS steps), column and row lists (one over three slabs), the split layout at 1135 accessions"""
-    exe = str(tmp_path / "kin_host_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-Wno-attributes",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "tests", "kin_host_shim"),
-                           "-I", os.path.join(ROOT, "snpmatch_amd", "csrc"), os.path.join(ROOT, "tests", "kin_host_driver.cpp"), "-o", exe])
-    # (a library the environment preloads may come before the ASan runtime: ASan copes as long as it does not replace malloc)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=900)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.strip().split("\n")
-    assert lines[-1] == "done fails=0"
-    cases = [ln for ln in lines if ln.startswith("case ")]
-    assert len(cases) == 44 and all(ln.endswith(" ok") for ln in cases)
+    slabs (whole chunks and single LDS steps), column and row lists (one over three slabs), the split layout at 1135 accessions;
+    and the slab plan alone at the grid.y cap and below one step"""
+    cases = host_kernel_util.run_driver("kin_host_driver", tmp_path)
+    assert len(cases) == 46 and sum(ln.startswith("case plan-") for ln in cases) == 2
     assert sum("slabs=2" in ln for ln in cases) == 2 and sum("slabs=3" in ln for ln in cases) == 1

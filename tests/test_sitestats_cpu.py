@@ -3,15 +3,15 @@
 ``nan`` where the reference has ``nan``); every refusal of ``snpm_panel_site_counts`` that needs no device; the layering of repeated
 columns in ``engine.site_counts`` and the ``sitestats`` subcommand with the twin in the place of the device call; and the kernel
 source itself, compiled for the host and run by 512 real threads per block under AddressSanitizer + UBSan
-(tests/site_host_driver.cpp, a child process)."""
+(tests/site_host_driver.cpp on tests/host_kernel/, a child process)."""
 import glob
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_kernel_util
 import sitestats_twin
 from snpmatch_amd import _lib, cli, engine
 from snpmatch_amd.core import sitestats, snp_genotype
@@ -388,19 +388,8 @@ def test_kernel_source_on_the_host_under_asan_and_ubsan(tmp_path):
     workspace: 1 / 2 / 31 / 32 / 33 / 63 / 64 / 65 / 130 / 1135 accessions x 0 / 1 / 63 / 64 / 65 rows in the three layouts (the
     split layout at 1135 accessions included), 1 / 2 / 3 / SNPM_SITE_MAX_GROUPS groups with an empty, a one-column and overlapping
     groups, rows of a pitch that takes the byte loads, a whole wave per row, a row list with repeats, two slabs"""
-    exe = str(tmp_path / "site_host_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-Wno-attributes",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "tests", "site_host_shim"),
-                           "-I", os.path.join(ROOT, "snpmatch_amd", "csrc"), os.path.join(ROOT, "tests", "site_host_driver.cpp"), "-o", exe])
-    # (a library the environment preloads may come before the ASan runtime: ASan copes as long as it does not replace malloc)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=900)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.strip().split("\n")
-    assert lines[-1] == "done fails=0"
-    cases = [ln for ln in lines if ln.startswith("case ")]
-    assert len(cases) == 62 and all(ln.endswith(" ok") for ln in cases)
+    cases = host_kernel_util.run_driver("site_host_driver", tmp_path)
+    assert len(cases) == 62
     assert sum("slabs=2" in ln for ln in cases) == 2 and sum("wide=0" in ln for ln in cases) >= 5
     assert {1, 8, 32, 64} <= set(int(ln.split("lanes=")[1].split()[0]) for ln in cases)       # lanes per row: a row per lane .. a whole wave
     assert sum("groups=32 " in ln for ln in cases) >= 10 and any("layout=2 acc=1135" in ln for ln in cases)
