@@ -430,7 +430,8 @@ int snpm_profile_enable(snpm_ctx *ctx, int on);
 int snpm_profile_reset(snpm_ctx *ctx);
 /* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t" (transpose of
    snpm_pair_counts), "pairs_c" (its count), "kin_planes" / "kin_count" (the two kernels of snpm_panel_kinship_counts),
-   "site_counts" (the kernel of snpm_panel_site_counts, one launch per slab).  Synchronises the stream. */
+   "site_counts" (the kernel of snpm_panel_site_counts, one launch per slab), "ld_planes" / "ld_band" (the two kernels of
+   snpm_panel_ld_band, one launch each per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -542,6 +543,45 @@ int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t nc
 #define SNPM_SITE_MAX_GROUPS 32
 int snpm_panel_site_counts(snpm_panel *panel, const int32_t *cols, const int64_t *grp_off, int64_t n_groups, const int64_t *row_idx,
                            int64_t row0, int64_t n_rows, int32_t *counts);
+
+/* ---------------------------------------------------------------- panel LD */
+/* Genotype.calculate_ld / calculate_ld (core/snp_genotype.py:291-295, :348-358 of the reference; neither runs there) on the
+   RESIDENT panel (int8 or packed): linkage disequilibrium of every selected row with each of the `band` rows after it, as one call.
+   Host pointers in and out.
+     cols [ncols]     distinct accession columns, any order; NULL = all accessions (ncols is ignored then)
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows) (row0 is ignored when
+                      row_idx is given).  Row k of the SELECTION is paired with rows k + 1 .. k + band of the selection
+     counts [n_rows][band][9]   per row k and offset d = 1 .. band (j = k + d), over the selected columns, with a = canonical code 1
+                      (alt), h = code 2 (het), m = code 0, 1 or 2 (an int8 panel's "other" code 3 and missing calls are outside m):
+                      n = |m_k & m_j|, Ak = |a_k & m_j|, Hk = |h_k & m_j|, Aj = |a_j & m_k|, Hj = |h_j & m_k|, AA = |a_k & a_j|,
+                      AH = |a_k & h_j|, HA = |h_k & a_j|, HH = |h_k & h_j|.  NULL = not wanted
+     r2 [n_rows][band]   squared Pearson correlation of the two rows' genotype values (v_alt for code 1, v_het for code 2, 0 for
+                      code 0; both 0 .. 3) over the n common columns, from exact integers:
+                        sx = v_alt Ak + v_het Hk, sxx = v_alt^2 Ak + v_het^2 Hk, sy / syy alike from Aj, Hj,
+                        sxy = v_alt^2 AA + v_alt v_het (AH + HA) + v_het^2 HH,
+                        num = n sxy - sx sy, dx = n sxx - sx^2, dy = n syy - sy^2   (int64),
+                        r2 = (double(num) * double(num)) / (double(dx) * double(dy))
+                      -- three correctly rounded operations, the same bits on every machine, never above 1.  NaN where n < min_n
+                      (min_n >= 1), where dx or dy is 0 (a row constant among the common columns).  NULL = not wanted
+   Cells with k + d >= n_rows hold zeros / NaN.  Every cell is written exactly once.
+   The row axis is processed in slabs whose planes (12 bytes per 32 columns and row, the `band` halo rows behind the slab included)
+   and outputs (44 bytes per cell) fit a workspace budget (256 MiB; SNPM_LD_WS_MB, read by snpm_init); a slab is a multiple of 64
+   rows, at least 64; two launches per slab.
+   Limits: panels of at most 16384 accessions; band <= SNPM_LD_MAX_BAND, which bounds what the smallest slab of 64 rows takes on the
+   device whatever the budget: 64 x 4096 cells x 44 bytes = 11 MiB of outputs and 64 + 4096 plane rows (25 MiB at 16384 accessions).
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size,
+   band, v_alt, v_het and min_n in range, not both outputs NULL when there is work -- these before the panel handle is looked at,
+   the message of a NULL panel is in snpm_last_error(NULL) -- then every column inside the panel, no column twice, every row inside
+   the panel, the panel's width.  n_rows == 0 returns without a launch and writes nothing.  Uploads into the panel that are still
+   in flight are waited for on the device. */
+#define SNPM_LD_MAX_BAND 4096
+int snpm_panel_ld_band(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                       int64_t band, int32_t v_alt, int32_t v_het, int32_t min_n, int32_t *counts, double *r2);
+/* Greedy marker pruning on a band of r2 values (host only, no context, no GPU), in row order: keep[k] = 1 when row k is eligible
+   (eligible == NULL: every row) and no KEPT row j in [k - band, k) has r2[j][k - j - 1] > threshold; else 0.  NaN never prunes.
+   r2 [n_rows][band] as snpm_panel_ld_band writes it; eligible, keep [n_rows] bytes.  SNPM_ERR_BADARG for a negative n_rows,
+   band < 1, or a NULL r2 / keep with n_rows > 0. */
+int snpm_ld_prune(int64_t n_rows, int64_t band, const double *r2, const uint8_t *eligible, double threshold, uint8_t *keep);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

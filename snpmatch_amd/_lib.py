@@ -52,6 +52,7 @@ SYMBOLS = [
     "snpm_pair_counts",
     "snpm_panel_kinship_counts",
     "snpm_panel_site_counts",
+    "snpm_panel_ld_band", "snpm_ld_prune",
 ]
 
 _lib = None
@@ -245,6 +246,8 @@ def load():
     lib.snpm_pair_counts.argtypes = [p, p, i64, ci, i64, p, ci, p, p]
     lib.snpm_panel_kinship_counts.argtypes = [p, p, i64, p, i64, i64, p, p, p]
     lib.snpm_panel_site_counts.argtypes = [p, p, p, i64, p, i64, i64, p]
+    lib.snpm_panel_ld_band.argtypes = [p, p, i64, p, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, p, p]
+    lib.snpm_ld_prune.argtypes = [i64, i64, p, p, C.c_double, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]
     lib.snpm_profile_enable.argtypes = [p, ci]
     lib.snpm_profile_reset.argtypes = [p]

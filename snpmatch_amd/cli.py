@@ -7,7 +7,8 @@ mode with the parents named as two accessions of the database (``-p 6091x6191``)
 (core/genotype_cross.py says why).  ``pairsnp`` compares two sample files as the reference does; ``pairsnp-batch`` compares every
 pair of a cohort in one device call.  ``kinship`` (not in the reference as a command) counts the relatedness of every pair of
 accessions of the database on the device and lists the near-identical ones; ``sitestats`` (not in the reference as a command
-either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter; ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of
+neighbouring DB rows inside a band on the device and prunes the rows by it.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
 path.
 """
 import argparse
@@ -109,6 +110,15 @@ def snpmatch_sitestats(args):
         if args[key]:
             check_file(args[key])
     sitestats.potatoSiteStats(args)
+
+
+def snpmatch_ld(args):
+    from .core import ld
+    check_file(args['hdf5File'])
+    for key in ('accFile', 'sitesFile'):
+        if args[key]:
+            check_file(args[key])
+    ld.potatoLD(args)
 
 
 def makedb_native(args):
@@ -240,6 +250,22 @@ def get_options(description, version_message):
     site.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     site.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.sitestats.npz, <prefix>.sitestats.json and, with a threshold, <prefix>.sites.tsv")
     site.set_defaults(func=snpmatch_sitestats)
+
+    # not in the reference as a command (its calculate_ld does not run): LD between neighbouring SNPs of the DB and pruning of a marker set by it
+    ldp = sub.add_parser('ld', help="linkage disequilibrium (r2) of every SNP with the SNPs after it inside a band, the decay curve, and LD pruning of the rows")
+    ldp.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    ldp.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    ldp.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    ldp.add_argument("--bed", dest="bed", default=None, help="only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
+    ldp.add_argument("--sites", dest="sitesFile", default=None, help="only the rows listed in a <prefix>.sites.tsv of sitestats (columns chr and pos)")
+    ldp.add_argument("--band", dest="band", default=50, type=int, help="pair every row with this many rows after it on its chromosome (default 50)")
+    ldp.add_argument("--window_bp", dest="window_bp", default=None, type=int, help="pairs further apart than this many bp count as undefined")
+    ldp.add_argument("--r2", dest="r2", default=0.2, type=float, help="prune a row whose r2 with an earlier kept row of the band exceeds this (default 0.2)")
+    ldp.add_argument("--min_n", dest="min_n", default=2, type=int, help="r2 is undefined with fewer accessions informative at both rows (default 2)")
+    ldp.add_argument("--keep_r2", action="store_true", dest="keep_r2", default=False, help="also write <prefix>.ld.npz: chr, pos, r2 [rows, band], keep")
+    ldp.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    ldp.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pruned.tsv and <prefix>.ld.json")
+    ldp.set_defaults(func=snpmatch_ld)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

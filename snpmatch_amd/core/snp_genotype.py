@@ -405,18 +405,7 @@ class Genotype(object):
         homozygous and different.  None = all accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a
         dense range."""
         from .. import engine
-        panel = self.panel()
-        if getattr(self, "_shard", None) is not None or not isinstance(panel, engine.Panel):
-            raise TypeError("kinship needs every accession column of the DB on one device: this DB is %s.  Run it in one process on "
-                            "one GPU with a DB that fits it (SNPMATCH_GPUS unset or one device, no torch.distributed launcher)"
-                            % ("spread over several GPUs by accession" if isinstance(panel, engine.GroupPanel) or
-                               getattr(self, "_shard", None) is not None else "streamed through the device in row slabs"))
-        rows = None
-        if filter_snp_ix is not None:
-            rows = np.asarray(filter_snp_ix, dtype=np.int64).reshape(-1)
-            if len(rows) and rows[0] >= 0 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))):
-                rows = range(int(rows[0]), int(rows[0]) + len(rows))
-        return engine.kinship_counts(panel, filter_acc_ix, rows)
+        return engine.kinship_counts(_resident_panel(self, "kinship needs"), filter_acc_ix, _rows_or_range(filter_snp_ix))
 
     def kinship_given_snps(self, filter_acc_ix=None, filter_snp_ix=None):
         """Kinship between all pairs of the listed accessions over the listed DB rows (core/snp_genotype.py:256-289): fp64 ndarray
@@ -435,17 +424,7 @@ class Genotype(object):
         G = 1), an index array (G = 1; a repeat counts as listed) or a dict name -> index array (G = len(dict), in the dict's
         order).  ``filter_snps_ix``: None = all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        panel = self.panel()
-        if getattr(self, "_shard", None) is not None or not isinstance(panel, engine.Panel):
-            raise TypeError("site statistics need every accession column of the DB on one device: this DB is %s.  Run it in one "
-                            "process on one GPU with a DB that fits it (SNPMATCH_GPUS unset or one device, no torch.distributed launcher)"
-                            % ("spread over several GPUs by accession" if isinstance(panel, engine.GroupPanel) or
-                               getattr(self, "_shard", None) is not None else "streamed through the device in row slabs"))
-        rows = None
-        if filter_snps_ix is not None:
-            rows = np.asarray(filter_snps_ix, dtype=np.int64).reshape(-1)
-            if len(rows) and rows[0] >= 0 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))):
-                rows = range(int(rows[0]), int(rows[0]) + len(rows))
+        panel, rows = _resident_panel(self, "site statistics need"), _rows_or_range(filter_snps_ix)
         if isinstance(filter_acc_ix, dict):
             for name, ix in filter_acc_ix.items():
                 assert type(ix) is np.ndarray, "provide numpy arrays in a dictionary when giving subpopulations (%r)" % (name,)
@@ -484,6 +463,44 @@ class Genotype(object):
         counts = self.site_counts(filter_acc_ix, filter_snps_ix)
         return counts[0, :, int(polarize_geno)] > float(n_listed) / 2
 
+    # ------------------------------------------------------------------ linkage disequilibrium
+    def ld_band(self, band, filter_acc_ix=None, filter_snps_ix=None, v_alt=2, v_het=1, min_n=2, counts=True, r2=True):
+        """``(counts, r2)`` of every listed DB row with each of the ``band`` listed rows after it, among the listed accessions,
+        computed on the resident panel in one call (``engine.ld_band``): int32 [n, band, 9] -- n, Ak, Hk, Aj, Hj, AA, AH, HA, HH --
+        and fp64 [n, band] (``ld_from_counts`` of them).  ``filter_acc_ix``: None = all accessions, else DISTINCT indices;
+        ``filter_snps_ix``: None = all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        return engine.ld_band(_resident_panel(self, "LD needs"), band, filter_acc_ix, _rows_or_range(filter_snps_ix), v_alt, v_het, min_n, counts, r2)
+
+    def calculate_ld(self, snp_ix, accs_ix=None, v_alt=2, v_het=1, min_n=2):
+        """The full symmetric r2 matrix, fp64 [n, n], of the listed DB rows among the listed accessions (core/snp_genotype.py:291-295
+        names it: the method there indexes the wrong axis and writes ``nan`` into an int8 array).  Built from ONE band call with
+        ``band = n - 1`` -- cell [k][d - 1] is the pair (k, k + d) -- and one ``site_counts`` call for the diagonal: 1, or nan
+        for a row that is constant among its informative accessions (or has fewer than ``min_n`` of them).  A missing call leaves
+        the PAIR's sum, not the whole matrix, as it would in the dense form.  Lists longer than ``engine.LD_MAX_BAND + 1`` rows are
+        refused: a dense matrix is the wrong shape for them, ``ld_band`` gives the band."""
+        from .. import engine
+        snp_ix = np.asarray(snp_ix, dtype=np.int64).reshape(-1)
+        n = len(snp_ix)
+        if n - 1 > engine.LD_MAX_BAND:
+            raise ValueError("calculate_ld builds a dense matrix from one band call and takes at most %d rows, got %d: ask ld_band "
+                             "for the band of a longer list" % (engine.LD_MAX_BAND + 1, n))
+        out = np.full((n, n), np.nan, dtype=np.float64)
+        if n == 0:
+            return out
+        site = self.site_counts(accs_ix, snp_ix)[0].astype(np.int64)
+        own = np.zeros((n, 9), dtype=np.int64)                      # a row paired with itself
+        own[:, 0] = site[:, 0] + site[:, 1] + site[:, 2]
+        own[:, 1] = own[:, 3] = own[:, 5] = site[:, 1]
+        own[:, 2] = own[:, 4] = own[:, 8] = site[:, 2]
+        out[np.arange(n), np.arange(n)] = ld_from_counts(own, v_alt, v_het, min_n)
+        if n > 1:
+            band = self.ld_band(n - 1, accs_ix, snp_ix, v_alt, v_het, min_n, counts=False)[1]
+            for d in range(1, n):
+                k = np.arange(n - d)
+                out[k, k + d] = out[k + d, k] = band[:n - d, d - 1]
+        return out
+
     # ------------------------------------------------------------------ --refine support
     def identify_segregating_snps(self, accs_ix):
         """DB rows where the given accessions do not all carry the same informative call
@@ -514,6 +531,30 @@ class Genotype(object):
             hi = np.where(seen, firsts, 0).max(axis=0)
             return both[:, 0, :].any(axis=0) | (seen.any(axis=0) & (lo != hi))
         return panel.segregating_rows(accs_ix)                      # one device scan over the listed columns (k_segregating)
+
+
+def _resident_panel(g, who_needs):
+    """the panel of a ``Genotype`` for a scan that needs every accession column on one device (kinship, site statistics, LD):
+    accession-sharded and streamed DBs are refused with the reason"""
+    from .. import engine
+    panel = g.panel()
+    if getattr(g, "_shard", None) is not None or not isinstance(panel, engine.Panel):
+        raise TypeError("%s every accession column of the DB on one device: this DB is %s.  Run it in one process on one GPU with a "
+                        "DB that fits it (SNPMATCH_GPUS unset or one device, no torch.distributed launcher)"
+                        % (who_needs, "spread over several GPUs by accession" if isinstance(panel, engine.GroupPanel) or
+                           getattr(g, "_shard", None) is not None else "streamed through the device in row slabs"))
+    return panel
+
+
+def _rows_or_range(snp_ix):
+    """a row filter for the panel scans: None (all rows), a ``range`` where the list is a run ``r, r + 1, ...`` (scanned as a dense
+    range), else the list as int64"""
+    if snp_ix is None:
+        return None
+    rows = np.asarray(snp_ix, dtype=np.int64).reshape(-1)
+    if len(rows) and rows[0] >= 0 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))):
+        return range(int(rows[0]), int(rows[0]) + len(rows))
+    return rows
 
 
 def kinship_from_counts(ninfo, same, diff):
@@ -581,6 +622,42 @@ def _polarize_snps(snps, polarize_geno=1, genotypes=[0, 1]):
     rows = out[flip]
     out[flip] = np.where(rows == first, second, np.where((rows == second) | (rows == 3), first, rows)).astype(out.dtype)
     return out
+
+
+def ld_from_counts(counts, v_alt=2, v_het=1, min_n=2):
+    """r2 from LD pair counts [..., 9] (n, Ak, Hk, Aj, Hj, AA, AH, HA, HH), the host form of what ``snpm_panel_ld_band`` computes:
+    with the genotype values ``v_alt`` for code 1 and ``v_het`` for code 2, int64 ``num = n sxy - sx sy``, ``dx = n sxx - sx^2``,
+    ``dy = n syy - sy^2`` and fp64 ``(num * num) / (dx * dy)`` -- three correctly rounded operations on exact integers, the
+    device's bits.  ``nan`` where ``n < min_n`` or a row is constant among the common columns."""
+    for name, v in (("v_alt", v_alt), ("v_het", v_het)):
+        if v not in (0, 1, 2, 3):
+            raise ValueError("%s must be 0 .. 3, got %r" % (name, v))
+    if min_n < 1:
+        raise ValueError("min_n must be at least 1, got %r" % (min_n,))
+    c = np.asarray(counts).astype(np.int64)
+    va, vh = int(v_alt), int(v_het)
+    n = c[..., 0]
+    sx, sy = va * c[..., 1] + vh * c[..., 2], va * c[..., 3] + vh * c[..., 4]
+    sxx, syy = va * va * c[..., 1] + vh * vh * c[..., 2], va * va * c[..., 3] + vh * vh * c[..., 4]
+    sxy = va * va * c[..., 5] + va * vh * (c[..., 6] + c[..., 7]) + vh * vh * c[..., 8]
+    num, dx, dy = n * sxy - sx * sy, n * sxx - sx * sx, n * syy - sy * sy
+    r2 = np.full(n.shape, np.nan, dtype=np.float64)
+    ok = (n >= min_n) & (dx != 0) & (dy != 0)
+    top, bottom = num[ok].astype(np.float64), dx[ok].astype(np.float64) * dy[ok].astype(np.float64)
+    r2[ok] = (top * top) / bottom
+    return r2
+
+
+def calculate_ld(snps):
+    """Squared Pearson correlation of every pair of rows of a small float matrix [n_snp, n_acc] on the host, with the semantics of
+    the reference's function of this name (core/snp_genotype.py:348-358, written there on scipy aliases that scipy has dropped):
+    rows are centred and scaled by their population standard deviation, multiplied out and squared.  A ``nan`` in a row, or a
+    constant row, makes that row and column ``nan``."""
+    x = np.asarray(snps, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = (x - x.mean(axis=1, keepdims=True)) / x.std(axis=1, keepdims=True)
+        r = (z @ z.T) / x.shape[1]
+    return r * r
 
 
 def _bare_chr_id(name):

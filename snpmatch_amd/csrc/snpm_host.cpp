@@ -1,5 +1,5 @@
 // snpm_host.cpp -- entry points of libsnpmatch_hip.so that are pure host code (no HIP, no context): caller-side index
-// preparation of the scoring path.  Compiled into the library by build_lib.sh and, together with
+// preparation of the scoring path, marker pruning on a band of r2 values.  Compiled into the library by build_lib.sh and, together with
 // snpm_vcf.cpp, into an AddressSanitizer / UBSan driver by the CPU test-suite (tests/test_host_sanitizers_cpu.py).
 #include <sched.h>
 
@@ -111,6 +111,21 @@ int snpm_intersect_sorted_search(const int64_t *a, int64_t na, const int64_t *b,
         k += cnt[(size_t)t];
     }
     *n_out = k;
+    return SNPM_OK;
+}
+
+// Greedy marker pruning on the band of r2 values that snpm_panel_ld_band writes (r2[j][d - 1] is rows j and j + d), in row order:
+// row k is kept when it is eligible and no KEPT row j of the `band` rows before it has r2[j][k - j - 1] > threshold.  A NaN
+// compares false: it never prunes.  Pure host code (no ctx).
+int snpm_ld_prune(int64_t n_rows, int64_t band, const double *r2, const uint8_t *eligible, double threshold, uint8_t *keep)
+{
+    if (n_rows < 0 || band < 1 || (n_rows > 0 && (!r2 || !keep))) return SNPM_ERR_BADARG;
+    for (int64_t k = 0; k < n_rows; ++k) {
+        uint8_t ok = eligible ? (uint8_t)(eligible[k] != 0) : (uint8_t)1;
+        for (int64_t j = std::max<int64_t>(0, k - band); ok && j < k; ++j)
+            if (keep[j] && r2[j * band + (k - j - 1)] > threshold) ok = 0;
+        keep[k] = ok;
+    }
     return SNPM_OK;
 }
 

@@ -833,6 +833,69 @@ def site_counts(panel, groups=None, rows=None):
     return out
 
 
+LD_MAX_BAND = 4096             # SNPM_LD_MAX_BAND: offsets of one ``snpm_panel_ld_band`` call
+
+
+def ld_slab_rows(ws_bytes, n_acc, band, n_rows):
+    """rows of one slab of an ``ld_band`` call under a workspace budget of ``ws_bytes`` (SNPM_LD_WS_MB): ``ld_slab_rows`` of
+    csrc/snpm_k_ld.hpp in Python, for tools and tests that want the plan (the host driver of the kernel prints the library's)"""
+    words = (n_acc + 31) // 32
+    per_row, halo = band * 44 + words * 12, band * words * 12
+    fit = (ws_bytes - halo) // per_row // 64 * 64 if ws_bytes > halo else 0
+    return min(max(fit, 64), n_rows)
+
+
+def ld_band(panel, band, cols=None, rows=None, v_alt=2, v_het=1, min_n=2, counts=True, r2=True):
+    """Linkage disequilibrium of every selected row of a resident panel with each of the ``band`` rows after it, in one device call
+    (``snpm_panel_ld_band``).  ``cols``: distinct accession indices, any order (None: all accessions; a repeat is refused);
+    ``rows``: panel rows as an index array, any order, repeats allowed, or a ``slice`` / ``range`` of step 1 (a dense range), or
+    None (all rows): row k of the SELECTION is paired with rows k + 1 .. k + band of it.  Returns ``(counts, r2)``: int32
+    [n_rows, band, 9] -- n, Ak, Hk, Aj, Hj, AA, AH, HA, HH over the selected columns (a = code 1, h = code 2, m = code 0 / 1 / 2) --
+    and fp64 [n_rows, band], the squared correlation of the genotype values (``v_alt`` for code 1, ``v_het`` for code 2; both
+    0..3), nan where fewer than ``min_n`` columns are informative in both rows or a row is constant among them.  Cells with k + d >=
+    n_rows are zero / nan.  ``counts=False`` / ``r2=False``: that array is not computed and None comes back in its place.  Only a
+    panel whose columns all live on one device can be asked: group (accession-sharded) and streamed panels are refused."""
+    _need_resident_panel(panel, "ld_band")
+    for name, v in (("band", band), ("v_alt", v_alt), ("v_het", v_het), ("min_n", min_n)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise TypeError("%s must be an integer, got %r" % (name, v))
+    if not 1 <= band <= LD_MAX_BAND:
+        raise AssertionError("band must be 1 .. %d (SNPM_LD_MAX_BAND), got %d" % (LD_MAX_BAND, band))
+    if not (counts or r2):
+        raise ValueError("ld_band: neither counts nor r2 wanted")
+    ncols = 0
+    if cols is not None:
+        cols = np.asarray(cols).reshape(-1)
+        if cols.dtype.kind not in "iu" and len(cols):
+            raise TypeError("accession indices must be integers, got %s" % cols.dtype)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    out_c = np.empty((n_rows, band, 9), dtype=np.int32) if counts else None
+    out_r = np.empty((n_rows, band), dtype=np.float64) if r2 else None
+    check(panel.ctx.lib.snpm_panel_ld_band(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, band, v_alt, v_het, min_n, ptr(out_c),
+                                           ptr(out_r)), panel.ctx.h)
+    return out_c, out_r
+
+
+def ld_prune(r2, eligible=None, threshold=0.2):
+    """Greedy marker pruning on a band of r2 values [n_rows, band] as ``ld_band`` returns it (``snpm_ld_prune``, host code): bool
+    [n_rows], row k kept when it is eligible (None: every row) and no kept row j of the ``band`` rows before it has
+    ``r2[j, k - j - 1] > threshold``.  nan never prunes."""
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    if r2.ndim != 2 or r2.shape[1] < 1:
+        raise ValueError("r2 must be [n_rows, band] with band >= 1, got shape %r" % (r2.shape,))
+    if eligible is not None:
+        eligible = np.ascontiguousarray(np.asarray(eligible).astype(bool).reshape(-1)).view(np.uint8)
+        if len(eligible) != len(r2):
+            raise ValueError("eligible must have one entry per row of r2")
+    keep = np.zeros(len(r2), dtype=np.uint8)
+    rc = _lib.load().snpm_ld_prune(len(r2), r2.shape[1], ptr(r2), ptr(eligible), float(threshold), ptr(keep))
+    if rc:
+        raise AssertionError("snpm_ld_prune refused its arguments (%d)" % rc)
+    return keep.astype(bool)
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the
