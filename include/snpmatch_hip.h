@@ -431,7 +431,8 @@ int snpm_profile_reset(snpm_ctx *ctx);
 /* kernel: "fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t" (transpose of
    snpm_pair_counts), "pairs_c" (its count), "kin_planes" / "kin_count" (the two kernels of snpm_panel_kinship_counts),
    "site_counts" (the kernel of snpm_panel_site_counts, one launch per slab), "ld_planes" / "ld_band" (the two kernels of
-   snpm_panel_ld_band, one launch each per slab).  Synchronises the stream. */
+   snpm_panel_ld_band, one launch each per slab), "win_planes" / "win_count" (the two kernels of snpm_panel_window_counts, one
+   launch each per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -582,6 +583,37 @@ int snpm_panel_ld_band(snpm_panel *panel, const int32_t *cols, int64_t ncols, co
    r2 [n_rows][band] as snpm_panel_ld_band writes it; eligible, keep [n_rows] bytes.  SNPM_ERR_BADARG for a negative n_rows,
    band < 1, or a NULL r2 / keep with n_rows > 0. */
 int snpm_ld_prune(int64_t n_rows, int64_t band, const double *r2, const uint8_t *eligible, double threshold, uint8_t *keep);
+
+/* ---------------------------------------------------------------- panel windows */
+/* Genotype.calculate_heterozygosity_windows / mismatch_between_accs (core/snp_genotype.py:297-345 of the reference) on the RESIDENT
+   panel (int8 or packed): per genome window the call counts of every listed accession column and the agreement counts of listed
+   pairs of columns, as one call.  Host pointers in and out.
+     cols [ncols]      accession columns, any order, repeats allowed; NULL = all accessions (ncols must then be the panel's count)
+     pair_a, pair_b [n_pairs]   pair i is columns cols[pair_a[i]] and cols[pair_b[i]]: indices INTO THE COLUMN LIST, 0 .. ncols - 1;
+                       a == b is allowed, (a, b) and (b, a) are both allowed
+     row_idx [n_rows]  panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows)
+     win_off [n_win + 1]   offsets into the SELECTED rows: starts at 0, never decreases, ends at n_rows; window w holds the selected
+                       rows [win_off[w], win_off[w + 1]).  Empty windows are allowed anywhere
+     acc_counts [n_win][ncols][4]   c0, c1, c2 = rows of the window with canonical code 0 / 1 / 2 in that column, ninfo = rows whose
+                       call is not missing (an int8 panel's "other" code 3 counts in ninfo and in none of c0 .. c2; negative int8
+                       values and the 2-bit value 3 are missing).  NULL = not wanted
+     pair_counts [n_pairs][n_win][4]   n = rows where both calls are 0, 1 or 2; eq = rows among those where the two codes are equal
+                       (het against het is equal); hom_same / hom_diff = rows where both are homozygous and equal / different
+                       (summed over the windows: same / diff of snpm_panel_kinship_counts).  NULL = not wanted
+   Integers only: het = c2 / ninfo and mismatch = 1 - eq / n are the caller's (snp_genotype.het_from_counts / mismatch_from_counts).
+   The selected rows are processed in slabs: accession-major bit-planes (4 bits per call, whole steps of 1024 rows, at least one)
+   plus the cells of the slab's windows fit a workspace budget (256 MiB; SNPM_WIN_WS_MB, read by snpm_init); two launches per slab,
+   its cells are added into the zeroed outputs on the host, so the result does not depend on the budget.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size,
+   win_off sound, not both outputs NULL when there is work, pair_a / pair_b given with n_pairs > 0, n_rows < 2^31,
+   ncols <= SNPM_WIN_MAX_ACCESSIONS (the grid of the plane kernel) -- these before the panel handle is looked at, the message of a
+   NULL panel is in snpm_last_error(NULL) -- then every column inside the panel, every pair index inside the column list, every row
+   inside the panel.  n_win == 0 or ncols == 0 writes nothing; n_rows == 0 writes zeros without a launch.  Uploads into the panel
+   that are still in flight are waited for on the device. */
+#define SNPM_WIN_MAX_ACCESSIONS 4194240
+int snpm_panel_window_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs,
+                             const int64_t *row_idx, int64_t row0, int64_t n_rows, const int64_t *win_off, int64_t n_win, int32_t *acc_counts,
+                             int32_t *pair_counts);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

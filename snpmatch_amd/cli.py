@@ -8,7 +8,8 @@ mode with the parents named as two accessions of the database (``-p 6091x6191``)
 pair of a cohort in one device call.  ``kinship`` (not in the reference as a command) counts the relatedness of every pair of
 accessions of the database on the device and lists the near-identical ones; ``sitestats`` (not in the reference as a command
 either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter; ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of
-neighbouring DB rows inside a band on the device and prunes the rows by it.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+neighbouring DB rows inside a band on the device and prunes the rows by it; ``windows`` (not in the reference as a command) counts, per genome window, the
+heterozygosity of every accession and the mismatch of listed pairs of accessions on the device.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
 path.
 """
 import argparse
@@ -119,6 +120,15 @@ def snpmatch_ld(args):
         if args[key]:
             check_file(args[key])
     ld.potatoLD(args)
+
+
+def snpmatch_windows(args):
+    from .core import windows
+    check_file(args['hdf5File'])
+    for key in ('accFile', 'pairsFile'):
+        if args[key]:
+            check_file(args[key])
+    windows.potatoWindows(args)
 
 
 def makedb_native(args):
@@ -266,6 +276,20 @@ def get_options(description, version_message):
     ldp.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     ldp.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pruned.tsv and <prefix>.ld.json")
     ldp.set_defaults(func=snpmatch_ld)
+
+    # not in the reference as a command (it has the two methods): per genome window, heterozygosity of the accessions and mismatch of pairs
+    win = sub.add_parser('windows', help="per genome window: heterozygosity of every accession of the DB and mismatch of listed pairs of accessions (e.g. the duplicates of kinship)")
+    win.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    win.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    win.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    win.add_argument("--pairs", dest="pairsFile", default=None, help="text file whose first two columns name pairs of the selected accessions (a <prefix>.duplicates.tsv of kinship goes straight in)")
+    win.add_argument("--pairs_only", action="store_true", dest="pairs_only", default=False, help="take the members of the pairs as the accessions")
+    win.add_argument("--genome", dest="genome", default="athaliana_tair10", help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
+    win.add_argument("-b", "--window_size", dest="binLen", default=300000, type=int, help="window length in bp (default 300000)")
+    win.add_argument("--min_sites", dest="min_sites", default=5, type=int, help="a window is judged with MORE than this many informative rows; het is nan otherwise (default 5, the reference's)")
+    win.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    win.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.windows.npz, <prefix>.het_windows.tsv, <prefix>.windows.json and, with --pairs, <prefix>.pair_windows.tsv")
+    win.set_defaults(func=snpmatch_windows)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -139,6 +139,33 @@ class Genome(object):
             for span, members in get_bins_echr(self.chrlen[chr_ix], g_snppos[mine], binLen, offset):
                 yield (chr_ix, span, members)
 
+    def get_window_rows(self, g, binLen):
+        """The windows of ``get_bins_genome(g, binLen)`` as arrays, in its order, without the member lists: ``(chr_ix, start, end,
+        first, last)``, int64 [n_windows] each -- window k of the genome covers positions start[k] .. end[k] of chromosome
+        chr_ix[k] and holds the DB rows first[k] .. last[k] - 1 (two ``searchsorted`` calls per chromosome).  The windows of a
+        chromosome follow each other in the rows: ``first[k + 1] == last[k]``.  A chromosome that the DB does not have gives
+        windows without rows (first == last == 0); DB rows past the last window of their chromosome, and rows of a chromosome
+        this genome does not have, are in no window.  The positions of a chromosome must be sorted and >= 1 (the member lists of
+        ``get_bins_genome`` also serve other inputs)."""
+        db_ids = _bare(g.chrs)
+        self._check(db_ids, "genotype hdf5 file")
+        positions, binLen = np.asarray(g.positions), int(binLen)
+        parts = []
+        for chr_ix, cid in enumerate(self.chrs_ids):
+            starts = np.arange(1, int(self.chrlen[chr_ix]), binLen, dtype=np.int64)
+            where = np.flatnonzero(db_ids == cid)
+            if len(where):
+                row0, row1 = int(g.chr_regions[where[0]][0]), int(g.chr_regions[where[0]][1])
+                here = positions[row0:row1]
+                if len(here) and (here[0] < 1 or bool(np.any(np.diff(here) < 0))):
+                    raise ValueError("the positions of chromosome %s are not sorted (or below 1): its windows are not row ranges" % self.chrs[chr_ix])
+                first = np.searchsorted(here, starts, side="left").astype(np.int64) + row0
+                last = np.searchsorted(here, starts + (binLen - 1), side="right").astype(np.int64) + row0
+            else:
+                first = last = np.zeros(len(starts), dtype=np.int64)
+            parts.append((np.full(len(starts), chr_ix, dtype=np.int64), starts, starts + (binLen - 1), first, last))
+        return tuple(np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, dtype=np.int64) for k in range(5))
+
     def window_table(self, binLen):
         """(chr_ix, start, end) of every window of the genome, in iteration order"""
         return [(c, s, s + int(binLen) - 1) for c in range(len(self.chrs_ids))

@@ -501,6 +501,76 @@ class Genotype(object):
                 out[k, k + d] = out[k + d, k] = band[:n - d, d - 1]
         return out
 
+    # ------------------------------------------------------------------ genome windows
+    def window_counts(self, win_off, filter_acc_ix=None, pairs=None, filter_snps_ix=None, acc_counts=True):
+        """``(acc, pair)`` per window of the listed DB rows, counted on the resident panel in one call (``engine.window_counts``):
+        int32 [n_win, n_acc, 4] -- c0, c1, c2, ninfo of every listed accession -- and int32 [n_pairs, n_win, 4] -- n, eq, hom_same,
+        hom_diff of every listed pair.  ``win_off`` [n_win + 1] cuts the LISTED rows into windows; ``pairs`` [n_pairs, 2] indexes
+        the accession list.  ``filter_snps_ix``: None = all rows, a ``range``, or a row list (a run ``r, r + 1, ...`` is scanned as
+        a dense range)."""
+        from .. import engine
+        rows = filter_snps_ix if isinstance(filter_snps_ix, range) else _rows_or_range(filter_snps_ix)
+        return engine.window_counts(_resident_panel(self, "window counts need"), win_off, filter_acc_ix, pairs, rows, acc_counts)
+
+    def genome_window_counts(self, genome_class, window_size, filter_acc_ix=None, pairs=None, acc_counts=True):
+        """The same over the windows of a genome (``Genome.get_window_rows``): ``((chr_ix, start, end, first, last), acc, pair)``
+        with one device call per chromosome, whose rows are a range.  A window without rows keeps zero counts."""
+        table = genome_class.get_window_rows(self.g, window_size)
+        chr_ix, first, last = table[0], table[3], table[4]
+        n_win = len(chr_ix)
+        n_acc = len(self.accessions) if filter_acc_ix is None else np.asarray(filter_acc_ix).size
+        acc = np.zeros((n_win, n_acc, 4), dtype=np.int32) if acc_counts else None
+        pair = None if pairs is None else np.zeros((len(np.asarray(pairs).reshape(-1, 2)), n_win, 4), dtype=np.int32)
+        for c in range(len(genome_class.chrs)):
+            w = np.flatnonzero(chr_ix == c)
+            if not len(w) or last[w[-1]] <= first[w[0]]:
+                continue
+            r0, r1 = int(first[w[0]]), int(last[w[-1]])
+            got_a, got_p = self.window_counts(np.append(first[w], r1) - r0, filter_acc_ix, pairs, range(r0, r1), acc_counts)
+            if acc_counts:
+                acc[w] = got_a
+            if pairs is not None:
+                pair[:, w] = got_p
+        return table, acc, pair
+
+    def calculate_heterozygosity_windows(self, genome_class, window_size, sample_ix=None):
+        """Called heterozygosity of the listed accessions in the windows of a genome (core/snp_genotype.py:332-345): a frame indexed
+        ``Chr1,1,300000``, one fp64 column per entry of ``sample_ix`` (None: all accessions), ``#het / #informative`` of the window's
+        rows, ``nan`` where no more than 5 rows are informative.  As in the reference the denominator counts every call >= 0, an
+        int8 DB's code 3 included.  The reference gathers the panel once per window; here the rows of a chromosome are read once on
+        the device for all its windows and the division is made once per cell from the same two integers."""
+        import pandas as pd
+        from . import genomes
+        assert type(genome_class) is genomes.Genome, "provide a genome class, snpmatch.genomes.Genome"
+        if sample_ix is None:
+            sample_ix = np.arange(len(self.accessions))
+        sample_ix = np.asarray(sample_ix).reshape(-1)
+        (chr_ix, start, end, _, _), acc, _ = self.genome_window_counts(genome_class, window_size, sample_ix)
+        beds = ["%s,%d,%d" % (genome_class.chrs[c], s, e) for c, s, e in zip(chr_ix.tolist(), start.tolist(), end.tolist())]
+        return pd.DataFrame(het_from_counts(acc, 5), index=beds, columns=sample_ix, dtype=float)
+
+    def mismatch_between_accs(self, acc_x_ix, acc_y_ix, bin_length=None, genome_class=None):
+        """Where two accessions differ (core/snp_genotype.py:297-330).  Without ``bin_length``: fp64 [n_snps], 1 where the two calls
+        are equal, 0 where they differ, ``nan`` where either is missing or above 2 -- host work on the two columns.  With
+        ``bin_length`` and a ``Genome``: a frame chr / start / end / mismatch, one row per window of the genome, ``mismatch = 1 -
+        #equal / #both called`` (``nan`` for a window where the two share no call), counted on the resident panel.  The reference
+        reads the column-chunked file here; both forms use the same matrix."""
+        if bin_length is None:
+            snps = self.g_acc.snps
+            x, y = (np.asarray(snps[:, int(ix)]).astype(np.int64).reshape(-1) for ix in (acc_x_ix, acc_y_ix))
+            out = (x == y).astype(np.float64)
+            out[(x < 0) | (x > 2) | (y < 0) | (y > 2)] = np.nan
+            return out
+        import pandas as pd
+        from . import genomes
+        assert type(bin_length) is int, "provide an interger for window length"
+        assert type(genome_class) is genomes.Genome, "provide genome class to determine windows in genome"
+        (chr_ix, start, end, _, _), _, pair = self.genome_window_counts(genome_class, bin_length, np.array([int(acc_x_ix), int(acc_y_ix)]),
+                                                                        [[0, 1]], acc_counts=False)
+        frame = pd.DataFrame({'chr': np.asarray(genome_class.chrs)[chr_ix].astype(object), 'start': start.astype(object), 'end': end.astype(object),
+                              'mismatch': mismatch_from_counts(pair[0]).astype(object)}, columns=['chr', 'start', 'end', 'mismatch'])
+        return frame
+
     # ------------------------------------------------------------------ --refine support
     def identify_segregating_snps(self, accs_ix):
         """DB rows where the given accessions do not all carry the same informative call
@@ -658,6 +728,24 @@ def calculate_ld(snps):
         z = (x - x.mean(axis=1, keepdims=True)) / x.std(axis=1, keepdims=True)
         r = (z @ z.T) / x.shape[1]
     return r * r
+
+
+def het_from_counts(counts, y_min=5):
+    """``c2 / ninfo`` of window counts [..., 4] (c0, c1, c2, ninfo) in fp64: one correctly rounded division, ``nan`` where ``ninfo <=
+    y_min`` -- the reference's ``np_get_fraction(.., y_min=5)``"""
+    counts = np.asarray(counts)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        het = counts[..., 2].astype(np.float64) / counts[..., 3].astype(np.float64)
+    return np.where(counts[..., 3] <= y_min, np.nan, het)
+
+
+def mismatch_from_counts(pair_counts):
+    """``1.0 - eq / n`` of pair window counts [..., 4] (n, eq, hom_same, hom_diff) in fp64: one division, then one subtraction --
+    what ``1 - np.nanmean(..)`` of the reference's 0 / 1 vector does; ``nan`` where ``n == 0``"""
+    pair_counts = np.asarray(pair_counts)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        frac = pair_counts[..., 1].astype(np.float64) / pair_counts[..., 0].astype(np.float64)
+    return np.where(pair_counts[..., 0] == 0, np.nan, 1.0 - frac)
 
 
 def _bare_chr_id(name):

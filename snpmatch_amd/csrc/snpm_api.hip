@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count"};
 
 struct Buf {
     void *p = nullptr;
@@ -62,6 +62,8 @@ struct Buf {
     X(ws_site_member) X(ws_site_out)                                                                                              \
     /* snpm_panel_ld_band (snpm_api_ld.hpp): membership words; planes [slab rows + band][3][words]; counts and r2 of a slab */   \
     X(ws_ld_member) X(ws_ld_planes) X(ws_ld_counts) X(ws_ld_r2)                                                                   \
+    /* snpm_panel_window_counts (snpm_api_win.hpp): bit-planes [4][cols_pad][W] and cells of a slab; column list; pa | pb; win_off */ \
+    X(ws_win_planes) X(ws_win_cells) X(ws_win_cols) X(ws_win_pairs) X(ws_win_off)                                                 \
     /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
     /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
     X(ws_rows)                                                                                                                    \
@@ -109,6 +111,7 @@ struct snpm_ctx {
     size_t kin_ws_bytes = size_t(512) << 20;    // SNPM_KIN_WS_MB: bit-planes of one row slab of snpm_panel_kinship_counts
     size_t site_ws_bytes = size_t(256) << 20;   // SNPM_SITE_WS_MB: counts of one row slab of snpm_panel_site_counts
     size_t ld_ws_bytes = size_t(256) << 20;     // SNPM_LD_WS_MB: planes, counts and r2 of one row slab of snpm_panel_ld_band
+    size_t win_ws_bytes = size_t(256) << 20;    // SNPM_WIN_WS_MB: planes and cells of one row slab of snpm_panel_window_counts
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -498,6 +501,7 @@ try {
     if (const char *s = getenv("SNPM_KIN_WS_MB")) ctx->kin_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_SITE_WS_MB")) ctx->site_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_LD_WS_MB")) ctx->ld_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_WIN_WS_MB")) ctx->win_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -645,6 +649,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_site.hpp"
 
 #include "snpm_api_ld.hpp"
+
+#include "snpm_api_win.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

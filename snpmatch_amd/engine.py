@@ -896,6 +896,82 @@ def ld_prune(r2, eligible=None, threshold=0.2):
     return keep.astype(bool)
 
 
+WIN_MAX_ACCESSIONS = 65535 * 64     # SNPM_WIN_MAX_ACCESSIONS: columns of one ``snpm_panel_window_counts`` call (the plane kernel's grid)
+WIN_STEP_ROWS = 1024                # rows of a plane step of ``k_win_planes``: a slab is whole steps
+
+
+def window_slabs(ws_bytes, ncols, cells_per_window, win_off, n_rows):
+    """the slabs of a ``window_counts`` call under a workspace budget of ``ws_bytes`` (SNPM_WIN_WS_MB) as ``(s0, steps, w_lo, n_w)``:
+    ``win_slab_steps`` of csrc/snpm_k_win.hpp in Python, for tools and tests that want the plan (the host driver of the kernel prints
+    the library's).  ``cells_per_window``: the columns plus the pairs asked for."""
+    win_off = [int(v) for v in win_off]
+    n_win = len(win_off) - 1
+    step_bytes, cell_bytes = 4 * (-(-ncols // 64) * 64) * 16 * 8, 16 * cells_per_window
+    out, s0, w_lo = [], 0, 0
+    while s0 < n_rows:
+        while w_lo < n_win - 1 and win_off[w_lo + 1] <= s0:
+            w_lo += 1
+        need, steps, w_end = -(-(n_rows - s0) // WIN_STEP_ROWS), 0, w_lo
+        while True:
+            s1, e = min(s0 + (steps + 1) * WIN_STEP_ROWS, n_rows), w_end
+            while e < n_win and win_off[e] < s1:
+                e += 1
+            if steps >= 1 and (steps + 1) * step_bytes + (e - w_lo) * cell_bytes > ws_bytes:
+                break
+            steps, w_end = steps + 1, e
+            if steps >= need:
+                break
+        out.append((s0, steps, w_lo, w_end - w_lo))
+        s0 += steps * WIN_STEP_ROWS
+    return out
+
+
+def window_counts(panel, win_off, cols=None, pairs=None, rows=None, acc_counts=True):
+    """Per genome window, the call counts of every listed accession column and the agreement counts of listed pairs of columns of
+    a resident panel, in one device call (``snpm_panel_window_counts``).  ``rows``: panel rows as an index array, any order, repeats
+    allowed, or a ``slice`` / ``range`` of step 1 (a dense range), or None (all rows); ``win_off`` [n_win + 1]: offsets into the
+    SELECTED rows, starting at 0, never decreasing, ending at their number -- window w holds the selected rows ``win_off[w] ..
+    win_off[w + 1] - 1``, empty windows are allowed.  ``cols``: accession indices, any order, repeats allowed (None: all);
+    ``pairs``: int [n_pairs, 2], indices INTO THE COLUMN LIST (``(a, a)`` and both orders of a pair are allowed), or None.
+    Returns ``(acc, pair)``: int32 [n_win, n_cols, 4] -- c0, c1, c2 (rows with code 0 / 1 / 2) and ninfo (rows with a call; an int8
+    panel's code 3 is informative and in none of c0..c2) -- or None with ``acc_counts=False``, and int32 [n_pairs, n_win, 4] -- n
+    (both calls 0 / 1 / 2), eq (equal codes among them), hom_same, hom_diff (both homozygous, equal / different) -- or None without
+    ``pairs``.  Only a panel whose columns all live on one device can be asked: group (accession-sharded) and streamed panels are
+    refused."""
+    _need_resident_panel(panel, "window_counts")
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.asarray(cols).reshape(-1)
+        if cols.dtype.kind not in "iu" and len(cols):
+            raise TypeError("accession indices must be integers, got %s" % cols.dtype)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        ncols = len(cols)
+    if ncols > WIN_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_WIN_MAX_ACCESSIONS)" % (ncols, WIN_MAX_ACCESSIONS))
+    pa = pb = None
+    n_pairs = 0
+    if pairs is not None:
+        pairs = np.asarray(pairs)
+        if pairs.dtype.kind not in "iu" and pairs.size:
+            raise TypeError("pairs must be integer indices into the column list, got %s" % pairs.dtype)
+        pairs = pairs.reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pairs[:, 0], dtype=np.int32), np.ascontiguousarray(pairs[:, 1], dtype=np.int32)
+        n_pairs = len(pa)
+    if not acc_counts and pairs is None:
+        raise ValueError("window_counts: neither acc_counts nor pairs wanted")
+    win_off = np.ascontiguousarray(win_off, dtype=np.int64).reshape(-1)
+    n_win = len(win_off) - 1
+    if n_win < 0:
+        raise ValueError("win_off holds n_win + 1 entries")
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    out_a = np.zeros((n_win, ncols, 4), dtype=np.int32) if acc_counts else None
+    out_p = np.zeros((n_pairs, n_win, 4), dtype=np.int32) if pairs is not None else None
+    check(panel.ctx.lib.snpm_panel_window_counts(panel.h, ptr(cols), ncols, ptr(pa), ptr(pb), n_pairs, ptr(row_idx), row0, n_rows,
+                                                 ptr(win_off), n_win, ptr(out_a), ptr(out_p)), panel.ctx.h)
+    return out_a, out_p
+
+
 def weight_codes(wei, table):
     """uint16 codes [n, 3] with table[codes] == wei bit for bit, or None when some weight is not in ``table``
     (float64 [<= 65536], e.g. ``pl_table()``).  A binary search per weight on the host; parsers that still hold the
