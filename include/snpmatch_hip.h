@@ -432,7 +432,8 @@ int snpm_profile_reset(snpm_ctx *ctx);
    snpm_pair_counts), "pairs_c" (its count), "kin_planes" / "kin_count" (the two kernels of snpm_panel_kinship_counts),
    "site_counts" (the kernel of snpm_panel_site_counts, one launch per slab), "ld_planes" / "ld_band" (the two kernels of
    snpm_panel_ld_band, one launch each per slab), "win_planes" / "win_count" (the two kernels of snpm_panel_window_counts, one
-   launch each per slab).  Synchronises the stream. */
+   launch each per slab), "f1x_count" (the count kernel of snpm_panel_f1_counts, one launch per slab; its planes are a
+   "win_planes" launch per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -614,6 +615,33 @@ int snpm_ld_prune(int64_t n_rows, int64_t band, const double *r2, const uint8_t 
 int snpm_panel_window_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs,
                              const int64_t *row_idx, int64_t row0, int64_t n_rows, const int64_t *win_off, int64_t n_win, int32_t *acc_counts,
                              int32_t *pair_counts);
+
+/* ---------------------------------------------------------------- f1search */
+/* The in-silico F1 of EVERY pair of listed accession columns scored against one sample's hard calls over panel rows -- the
+   exhaustive form of CrossIdentifier.match_insilico_f1s (core/csmatch.py:106-129 of the reference, which crosses the ten best single
+   accessions only: snpm_query_f1_pairs) -- on the RESIDENT panel (int8 or packed), as one call.  Host pointers in and out.
+     cols [ncols]     accession columns, any order, repeats allowed; NULL = all accessions (ncols must then be the panel's count)
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows)
+     sample_class [n_rows]   the sample's class at every selected row: 0 ref, 1 alt, 2 het, 0xFF no class
+   The F1 of columns a, b at a row follows the rules of snpm_query_f1_pairs on canonical DB codes (0, 1, 2, 3 = an int8 panel's
+   "other" code, missing): ref when both are 0, alt when both are 1, het when both are not missing and the codes differ,
+   uninformative otherwise (a call missing, 2 with 2, 3 with 3).
+     ninfo [ncols, ncols]   rows where the F1 is ref, alt or het (rows of class 0xFF included)
+     hits  [ncols, ncols]   rows where the F1's class is the sample's class
+   Both are full symmetric matrices of exact int32 counts; the diagonal is the cross of a column with itself.  With the one-hot
+   weights of a hard-called sample (ParseInputs.get_wei_from_GT) hits[a][b] IS the reference's score of the pair and ninfo its
+   numinfo.  The row axis is processed in slabs whose bit-planes (4 bits per call) fit a workspace budget (512 MiB; SNPM_F1X_WS_MB,
+   read by snpm_init); two launches per slab, the counts accumulate on the device, so the result does not depend on the budget.
+   Limits: ncols <= SNPM_F1X_MAX_ACCESSIONS (each result matrix stays below 2^27 cells and the tile pairs of the count kernel below
+   2^16), n_rows < 2^31 (the counts are int32).
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, the
+   limits, non-NULL outputs when ncols > 0, non-NULL sample_class when n_rows > 0, every class byte 0, 1, 2 or 0xFF -- these before
+   the panel handle is looked at, the message of a NULL panel is in snpm_last_error(NULL) -- then every column and row inside the
+   panel, then ncols == the panel's accession count when cols is NULL.  ncols == 0 writes nothing; n_rows == 0 writes zeros without
+   a launch.  Uploads into the panel that are still in flight are waited for on the device. */
+#define SNPM_F1X_MAX_ACCESSIONS 11552
+int snpm_panel_f1_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                         const uint8_t *sample_class, int32_t *hits, int32_t *ninfo);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

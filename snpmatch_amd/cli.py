@@ -9,7 +9,8 @@ pair of a cohort in one device call.  ``kinship`` (not in the reference as a com
 accessions of the database on the device and lists the near-identical ones; ``sitestats`` (not in the reference as a command
 either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter; ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of
 neighbouring DB rows inside a band on the device and prunes the rows by it; ``windows`` (not in the reference as a command) counts, per genome window, the
-heterozygosity of every accession and the mismatch of listed pairs of accessions on the device.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+heterozygosity of every accession and the mismatch of listed pairs of accessions on the device; ``f1search`` (not in the reference) scores
+the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
 path.
 """
 import argparse
@@ -129,6 +130,15 @@ def snpmatch_windows(args):
         if args[key]:
             check_file(args[key])
     windows.potatoWindows(args)
+
+
+def snpmatch_f1search(args):
+    from .core import f1search
+    check_file(args['inFile'])
+    check_file(args['hdf5File'])
+    if args['accFile']:
+        check_file(args['accFile'])
+    f1search.potatoF1Search(args)
 
 
 def makedb_native(args):
@@ -290,6 +300,18 @@ def get_options(description, version_message):
     win.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     win.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.windows.npz, <prefix>.het_windows.tsv, <prefix>.windows.json and, with --pairs, <prefix>.pair_windows.tsv")
     win.set_defaults(func=snpmatch_windows)
+
+    # not in the reference (its match_insilico_f1s crosses the ten best single accessions): the in-silico F1 of every pair of accessions
+    f1s = sub.add_parser('f1search', help="parents of an F1 sample: the in-silico F1 of EVERY pair of accessions of the database scored against the sample")
+    f1s.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF/BED file for the variants in the sample")
+    f1s.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    f1s.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    f1s.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession name per line (default: all accessions)")
+    f1s.add_argument("--top", dest="top", default=10, type=int, help="pairs of the shortlist, re-scored with the sample's weights (default 10, at most 16)")
+    f1s.add_argument("--min_sites", dest="min_sites", default=100, type=int, help="a pair is ranked only with this many informative rows or more (default 100)")
+    f1s.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    f1s.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.f1search.scores.txt, <prefix>.f1search.npz and <prefix>.f1search.json")
+    f1s.set_defaults(func=snpmatch_f1search)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -417,6 +417,14 @@ class Genotype(object):
         ninfo, same, diff = self.kinship_counts(filter_acc_ix, filter_snp_ix)
         return kinship_from_counts(ninfo, same, diff)
 
+    def f1_counts(self, sample_class, filter_acc_ix=None, filter_snp_ix=None):
+        """(hits, ninfo) int32 [n, n] of the in-silico F1 of every pair of the listed accessions against a sample's hard calls
+        over the listed DB rows, counted on the resident panel (``engine.f1_counts``).  ``sample_class``: uint8, one class per
+        listed row (0 ref, 1 alt, 2 het, 0xFF none).  None = all accessions / all rows; a row list that is a run ``r, r + 1, ...``
+        is scanned as a dense range."""
+        from .. import engine
+        return engine.f1_counts(_resident_panel(self, "the exhaustive F1 search needs"), sample_class, filter_acc_ix, _rows_or_range(filter_snp_ix))
+
     # ------------------------------------------------------------------ site statistics
     def site_counts(self, filter_acc_ix=None, filter_snps_ix=None):
         """int32 [G, n, 4] -- c0, c1, c2 (listed accessions with code 0 / 1 / 2) and ninfo (listed accessions with a call) of every

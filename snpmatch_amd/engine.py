@@ -776,6 +776,34 @@ def kinship_counts(panel, cols=None, rows=None):
     return ninfo, same, diff
 
 
+F1X_MAX_ACCESSIONS = 11552     # SNPM_F1X_MAX_ACCESSIONS: columns of one ``f1_counts`` call
+F1X_NO_CLASS = 0xFF            # a row of the sample without a class: counted in ninfo only
+
+
+def f1_counts(panel, sample_class, cols=None, rows=None):
+    """The in-silico F1 of every pair of accession columns of a resident panel scored against one sample's hard calls, in one device
+    call (``snpm_panel_f1_counts``).  ``sample_class``: uint8, one class per selected row -- 0 ref, 1 alt, 2 het, 0xFF none;
+    ``cols`` / ``rows`` as for ``kinship_counts``.  Returns ``(hits, ninfo)``, int32 [n_cols, n_cols], full and symmetric: rows
+    where the F1 of the two columns (ref where both are 0, alt where both are 1, het where both are called and differ) has the
+    sample's class, and rows where it is informative at all.  With one-hot weights ``hits`` is the reference's score of the pair
+    (core/csmatch.py:115-125) and ``ninfo`` its numinfo.  Group (accession-sharded) and streamed panels are refused."""
+    _need_resident_panel(panel, "f1_counts")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    sample_class = np.ascontiguousarray(sample_class, dtype=np.uint8).reshape(-1)
+    assert len(sample_class) == n_rows, "one sample class per selected row: %d classes, %d rows" % (len(sample_class), n_rows)
+    if ncols > F1X_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_F1X_MAX_ACCESSIONS)" % (ncols, F1X_MAX_ACCESSIONS))
+    hits, ninfo = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(2))
+    check(ctx.lib.snpm_panel_f1_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(sample_class), ptr(hits), ptr(ninfo)), ctx.h)
+    return hits, ninfo
+
+
 SITE_MAX_GROUPS = 32           # SNPM_SITE_MAX_GROUPS: groups of one ``snpm_panel_site_counts`` call
 
 
