@@ -433,7 +433,8 @@ int snpm_profile_reset(snpm_ctx *ctx);
    "site_counts" (the kernel of snpm_panel_site_counts, one launch per slab), "ld_planes" / "ld_band" (the two kernels of
    snpm_panel_ld_band, one launch each per slab), "win_planes" / "win_count" (the two kernels of snpm_panel_window_counts, one
    launch each per slab), "f1x_count" (the count kernel of snpm_panel_f1_counts, one launch per slab; its planes are a
-   "win_planes" launch per slab).  Synchronises the stream. */
+   "win_planes" launch per slab), "par_count" (the count kernel of snpm_panel_parent_counts, one launch per slab of whole windows
+   and 65535 groups; its planes are a "win_planes" launch per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -642,6 +643,37 @@ int snpm_panel_window_counts(snpm_panel *panel, const int32_t *cols, int64_t nco
 #define SNPM_F1X_MAX_ACCESSIONS 11552
 int snpm_panel_f1_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                          const uint8_t *sample_class, int32_t *hits, int32_t *ninfo);
+
+/* ---------------------------------------------------------------- parentsearch */
+/* EVERY pair of listed accession columns scored, genome window by genome window, as the two parents of a RECOMBINANT sample (an F2,
+   a backcross, a RIL with residual heterozygosity: in one stretch of the genome parent A, in the next the F1 of A and B, in the next
+   parent B) against the sample's hard calls, on the RESIDENT panel (int8 or packed), as one call.  Host pointers in and out.
+     cols, row_idx / row0 / n_rows, sample_class   as for snpm_panel_f1_counts
+     win_off [n_win + 1]   offsets into the SELECTED rows: starts at 0, never decreases, ends at n_rows; window w holds the selected
+                       rows [win_off[w], win_off[w + 1]).  Empty windows are allowed anywhere; a window may start and end anywhere
+     min_win_sites     a window is used for a cell only with this many rows or more (>= 1)
+   Per cell (a, b) -- positions in the column list -- and window, over the rows where the F1 of a and b is informative (the rule of
+   snpm_panel_f1_counts) AND the sample has a class: n = those rows, hA / hB = rows among them where a's / b's canonical code is the
+   sample's class (0 / 1 / 2; code 3 never), hF = rows where the F1's class is the sample's class.  A window with n < min_win_sites
+   adds nothing to the cell.  Otherwise, with hom = max(hA, hB): if hF > hom the window is taken as the F1 (score += hF, w_het += 1),
+   else as a parent (score += hom; the window counts in w_first[a][b] when hA > hB, or hA == hB and a <= b, and in w_first[b][a]
+   otherwise); n_tot += n.
+     score, n_tot, w_first, w_het [ncols, ncols]   exact int32.  score, n_tot and w_het are symmetric; for a != b
+                       w_first[a][b] + w_first[b][a] + w_het[a][b] is the number of windows used for the pair; on the diagonal
+                       w_het is 0 and w_first the number of used windows.
+   The windows are processed in slabs of WHOLE windows whose bit-planes (4 bits per call) fit a workspace budget (512 MiB;
+   SNPM_PAR_WS_MB, read by snpm_init; a window larger than the budget is a slab of its own); the counts accumulate on the device, so
+   the result does not depend on the budget.  The host folds the window boundaries into a stream of masked 64-row segments (32
+   bytes per segment, at most one per 64 rows plus one per window).  Limits: those of snpm_panel_f1_counts.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size,
+   n_win >= 0, min_win_sites >= 1, the limits, win_off sound, non-NULL outputs when ncols > 0, non-NULL sample_class when n_rows > 0,
+   every class byte 0, 1, 2 or 0xFF -- these before the panel handle is looked at, the message of a NULL panel is in
+   snpm_last_error(NULL) -- then every column and row inside the panel, then ncols == the panel's accession count when cols is NULL.
+   ncols == 0 writes nothing; n_rows == 0 writes zeros without a launch.  Uploads into the panel that are still in flight are waited
+   for on the device. */
+int snpm_panel_parent_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                             const uint8_t *sample_class, const int64_t *win_off, int64_t n_win, int32_t min_win_sites, int32_t *score,
+                             int32_t *n_tot, int32_t *w_first, int32_t *w_het);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

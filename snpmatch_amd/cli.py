@@ -10,7 +10,8 @@ accessions of the database on the device and lists the near-identical ones; ``si
 either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter; ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of
 neighbouring DB rows inside a band on the device and prunes the rows by it; ``windows`` (not in the reference as a command) counts, per genome window, the
 heterozygosity of every accession and the mismatch of listed pairs of accessions on the device; ``f1search`` (not in the reference) scores
-the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles; ``parentsearch`` (not in the reference)
+scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
 path.
 """
 import argparse
@@ -139,6 +140,15 @@ def snpmatch_f1search(args):
     if args['accFile']:
         check_file(args['accFile'])
     f1search.potatoF1Search(args)
+
+
+def snpmatch_parentsearch(args):
+    from .core import parentsearch
+    check_file(args['inFile'])
+    check_file(args['hdf5File'])
+    if args['accFile']:
+        check_file(args['accFile'])
+    parentsearch.potatoParentSearch(args)
 
 
 def makedb_native(args):
@@ -312,6 +322,21 @@ def get_options(description, version_message):
     f1s.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     f1s.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.f1search.scores.txt, <prefix>.f1search.npz and <prefix>.f1search.json")
     f1s.set_defaults(func=snpmatch_f1search)
+
+    # not in the reference (its cross guesses the parents of an F2 from the single accessions that win clean windows): every pair per window
+    par = sub.add_parser('parentsearch', help="parents of a recombinant sample (F2, backcross): EVERY pair of accessions of the database scored per genome window as parent A, parent B or their F1")
+    par.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF/BED file for the variants in the sample")
+    par.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    par.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    par.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession name per line (default: all accessions)")
+    par.add_argument("--genome", dest="genome", default="athaliana_tair10", help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
+    par.add_argument("-b", "--binLength", dest="binLen", default=300000, type=int, help="window length in bp (default 300000)")
+    par.add_argument("--top", dest="top", default=10, type=int, help="pairs of the shortlist, with their window tracks (default 10, at most 16)")
+    par.add_argument("--min_sites", dest="min_sites", default=100, type=int, help="a pair is ranked only with this many rows or more in its used windows (default 100)")
+    par.add_argument("--min_win_sites", dest="min_win_sites", default=5, type=int, help="a window is used for a pair only with this many informative rows or more (default 5)")
+    par.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    par.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.parentsearch.json, <prefix>.parentsearch.npz and <prefix>.parentsearch.windows.tsv")
+    par.set_defaults(func=snpmatch_parentsearch)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

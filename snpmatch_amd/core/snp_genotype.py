@@ -425,6 +425,15 @@ class Genotype(object):
         from .. import engine
         return engine.f1_counts(_resident_panel(self, "the exhaustive F1 search needs"), sample_class, filter_acc_ix, _rows_or_range(filter_snp_ix))
 
+    def parent_counts(self, sample_class, win_off, min_win_sites=1, filter_acc_ix=None, filter_snp_ix=None):
+        """(score, n_tot, w_first, w_het) int32 [n, n] of every pair of the listed accessions taken, window by window, as the parents
+        of a recombinant sample, over the listed DB rows grouped into windows by ``win_off``, counted on the resident panel
+        (``engine.parent_counts``).  ``sample_class``: uint8, one class per listed row (0 ref, 1 alt, 2 het, 0xFF none).  None = all
+        accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        return engine.parent_counts(_resident_panel(self, "the parent search needs"), sample_class, win_off, min_win_sites, filter_acc_ix,
+                                    _rows_or_range(filter_snp_ix))
+
     # ------------------------------------------------------------------ site statistics
     def site_counts(self, filter_acc_ix=None, filter_snps_ix=None):
         """int32 [G, n, 4] -- c0, c1, c2 (listed accessions with code 0 / 1 / 2) and ninfo (listed accessions with a call) of every

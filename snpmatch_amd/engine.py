@@ -804,6 +804,37 @@ def f1_counts(panel, sample_class, cols=None, rows=None):
     return hits, ninfo
 
 
+def parent_counts(panel, sample_class, win_off, min_win_sites=1, cols=None, rows=None):
+    """Every pair of accession columns of a resident panel scored, window by window, as the two parents of a recombinant sample (an
+    F2, a backcross, a RIL with residual heterozygosity) against the sample's hard calls, in one device call
+    (``snpm_panel_parent_counts``).  ``sample_class`` / ``cols`` / ``rows`` as for ``f1_counts``; ``win_off`` [n_win + 1]: offsets
+    into the SELECTED rows (starts at 0, never decreases, ends at the row count; empty windows allowed); ``min_win_sites`` >= 1.
+    Per cell (a, b) -- positions in the column list -- and window, over the rows where the F1 of the two columns is informative and
+    the sample has a class: n such rows, of which hA / hB carry the sample's class in column a / b and hF in their F1.  A window
+    with n < min_win_sites is not used; otherwise it adds max(hA, hB, hF) to the score and n to n_tot, and counts as the F1 (hF
+    strictly the largest), or as the parent that fits better (a tie to the smaller position).  Returns ``(score, n_tot, w_first,
+    w_het)``, int32 [n_cols, n_cols]: ``w_first[a, b]`` windows taken as column a, ``w_first[b, a]`` as column b, ``w_het`` as
+    their F1.  Group (accession-sharded) and streamed panels are refused."""
+    _need_resident_panel(panel, "parent_counts")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    sample_class = np.ascontiguousarray(sample_class, dtype=np.uint8).reshape(-1)
+    assert len(sample_class) == n_rows, "one sample class per selected row: %d classes, %d rows" % (len(sample_class), n_rows)
+    win_off = np.ascontiguousarray(win_off, dtype=np.int64).reshape(-1)
+    assert len(win_off) >= 1, "win_off holds n_win + 1 entries"
+    if ncols > F1X_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_F1X_MAX_ACCESSIONS)" % (ncols, F1X_MAX_ACCESSIONS))
+    score, n_tot, w_first, w_het = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(4))
+    check(ctx.lib.snpm_panel_parent_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(sample_class), ptr(win_off), len(win_off) - 1,
+                                           int(min_win_sites), ptr(score), ptr(n_tot), ptr(w_first), ptr(w_het)), ctx.h)
+    return score, n_tot, w_first, w_het
+
+
 SITE_MAX_GROUPS = 32           # SNPM_SITE_MAX_GROUPS: groups of one ``snpm_panel_site_counts`` call
 
 
