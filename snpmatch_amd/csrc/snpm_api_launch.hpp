@@ -94,7 +94,13 @@ FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint,
     return g;
 }
 
-template <bool SKIP, bool GATHER>
+// an int8 panel whose rows end in a cache line (128 B) of padding only: k_fast<..., PAD> does not fetch it
+static inline bool fast_has_pad_line(const snpm_panel *p)
+{
+    return p->pitch - (p->n_acc + 127) / 128 * 128 >= 128;
+}
+
+template <bool SKIP, bool GATHER, bool PAD>
 int launch_fast_t(snpm_query *q, const FastGeom &g)
 {
     snpm_ctx *ctx = q->panel->ctx;
@@ -103,12 +109,12 @@ int launch_fast_t(snpm_query *q, const FastGeom &g)
     dim3 block(WAVE * g.wpb);
     ProfScope ps(ctx, PK_FAST);
     if (g.tile_rows == LONG_TILE_ROWS)          // long scans: tiles of LONG_TILE_ROWS rows (fast_tile_rows)
-        hipLaunchKernelGGL((k_fast<SKIP, GATHER, false, LONG_TILE_ROWS>), grid, block, 0, ctx->stream, p->d,
+        hipLaunchKernelGGL((k_fast<SKIP, GATHER, false, LONG_TILE_ROWS, PAD>), grid, block, 0, ctx->stream, p->d,
                            p->pitch, q->d_row_idx, q->row0, q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p,
-                           p->ld, (const int64_t *)nullptr);
+                           p->ld, p->n_acc, (const int64_t *)nullptr);
     else
-        hipLaunchKernelGGL((k_fast<SKIP, GATHER>), grid, block, 0, ctx->stream, p->d, p->pitch, q->d_row_idx, q->row0,
-                           q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld,
+        hipLaunchKernelGGL((k_fast<SKIP, GATHER, false, TILE_ROWS, PAD>), grid, block, 0, ctx->stream, p->d, p->pitch, q->d_row_idx, q->row0,
+                           q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, p->n_acc,
                            (const int64_t *)nullptr, g.tile_rows < TILE_ROWS ? g.tile_rows : 0);
     HIPCHK(ctx, hipGetLastError());
     return SNPM_OK;
@@ -116,9 +122,14 @@ int launch_fast_t(snpm_query *q, const FastGeom &g)
 
 int launch_fast_b(snpm_query *q, const FastGeom &g, bool skip, bool gather)
 {
+    if (fast_has_pad_line(q->panel)) {
+        if (skip)
+            return gather ? launch_fast_t<true, true, true>(q, g) : launch_fast_t<true, false, true>(q, g);
+        return gather ? launch_fast_t<false, true, true>(q, g) : launch_fast_t<false, false, true>(q, g);
+    }
     if (skip)
-        return gather ? launch_fast_t<true, true>(q, g) : launch_fast_t<true, false>(q, g);
-    return gather ? launch_fast_t<false, true>(q, g) : launch_fast_t<false, false>(q, g);
+        return gather ? launch_fast_t<true, true, false>(q, g) : launch_fast_t<true, false, false>(q, g);
+    return gather ? launch_fast_t<false, true, false>(q, g) : launch_fast_t<false, false, false>(q, g);
 }
 
 // block shape of k_fast_packed_q4 (a wave covers 1024 accessions): see run_fast

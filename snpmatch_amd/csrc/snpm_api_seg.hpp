@@ -56,15 +56,21 @@ static int launch_fast_seg(snpm_ctx *ctx, const SegJob &j, dim3 grid, dim3 block
     snpm_panel *p = j.p;
     const bool gather = j.d_row_idx != nullptr;
     ProfScope ps(ctx, PK_FAST);
+#define LAUNCH_SEG_P(S, G, PAD)                                                                                   \
+    hipLaunchKernelGGL((k_fast<S, G, true, TILE_ROWS, PAD>), grid, block, 0, ctx->stream, p->d, p->pitch, j.d_row_idx, j.row0, \
+                       n_parts, j.d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, \
+                       p->n_acc, d_desc)
 #define LAUNCH_SEG(S, G)                                                                                          \
-    hipLaunchKernelGGL((k_fast<S, G, true>), grid, block, 0, ctx->stream, p->d, p->pitch, j.d_row_idx, j.row0,    \
-                       n_parts, j.d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p, p->ld, d_desc)
+    do {                                                                                                          \
+        if (fast_has_pad_line(p)) LAUNCH_SEG_P(S, G, true); else LAUNCH_SEG_P(S, G, false);                       \
+    } while (0)
     if (j.skip) {
         if (gather) LAUNCH_SEG(true, true); else LAUNCH_SEG(true, false);
     } else {
         if (gather) LAUNCH_SEG(false, true); else LAUNCH_SEG(false, false);
     }
 #undef LAUNCH_SEG
+#undef LAUNCH_SEG_P
     HIPCHK(ctx, hipGetLastError());
     return SNPM_OK;
 }

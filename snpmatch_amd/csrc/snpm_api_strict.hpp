@@ -137,7 +137,15 @@ int run_strict_sparse(snpm_query *q, int skip, int64_t chunk, const int32_t *d_c
     const bool gather = q->d_row_idx != nullptr;
     const int64_t total = n_seg * ld;
     if (total > 0) {
-        dim3 sgrid((unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)ctx->n_cu * 8));     // grid-stride over (segment, column)
+        // grid-stride over (segment, column).  The host sizes the grid for REEVAL_CAP columns per segment (the count lives on the
+        // device), so the switch depends on the segments alone: n_seg > 4 * n_cu, whatever the number of flagged columns.
+        // Such long segment lists (more four-wave blocks than CUs) run in ONE-wave blocks: a short
+        // list of columns (2 flagged accessions x 20 019 chunks are 626 waves) then spreads over every CU instead of filling the
+        // first 157 blocks of a grid of four-wave blocks (1.09 -> 0.88 ms per 20M-row slab).  Short lists keep four-wave blocks:
+        // a lane's chain of row batches bounds the kernel either way (200 chunks: 12.5 us both ways), and the resident query's
+        // re-run measured 3 us more in the fast pass that FOLLOWS the one-wave grid (int8 and packed alike)
+        const int sthr = total > (int64_t)256 * ctx->n_cu ? WAVE : 256;
+        dim3 sgrid((unsigned)std::min<int64_t>((total + sthr - 1) / sthr, (int64_t)ctx->n_cu * (2048 / sthr)));
         const bool use_T = !q->transient_panel && q->n >= ctx->acc_major_min_rows && p->dT_state == 1;
         ProfScope ps(ctx, PK_STRICT);
         if (single_accession(p)) {
@@ -150,7 +158,7 @@ int run_strict_sparse(snpm_query *q, int skip, int64_t chunk, const int32_t *d_c
         } else if (use_T) {
             q->reeval_path = 1;
 #define LAUNCH_SPARSE_T(S, G)                                                                                      \
-    hipLaunchKernelGGL((k_strict_sparse_T<S, G>), sgrid, dim3(256), 0, ctx->stream, p->dT, p->pitchT, q->d_row_idx, \
+    hipLaunchKernelGGL((k_strict_sparse_T<S, G>), sgrid, dim3(sthr), 0, ctx->stream, p->dT, p->pitchT, q->d_row_idx, \
                        q->row0, q->d_w, d_seg_off, chunk, q->n, n_seg, d_cols, d_ncols, REEVAL_CAP, \
                        (double *)ctx->ws_seg_score.p, (uint32_t *)ctx->ws_seg_miss.p, ld)
             if (skip) {
@@ -162,7 +170,7 @@ int run_strict_sparse(snpm_query *q, int skip, int64_t chunk, const int32_t *d_c
         } else {
             q->reeval_path = 2;
 #define LAUNCH_SPARSE(S, G)                                                                                        \
-    hipLaunchKernelGGL((k_strict_sparse<S, G>), sgrid, dim3(256), 0, ctx->stream, p->d, p->kpitch, p->desc, q->d_row_idx, \
+    hipLaunchKernelGGL((k_strict_sparse<S, G>), sgrid, dim3(sthr), 0, ctx->stream, p->d, p->kpitch, p->desc, q->d_row_idx, \
                        q->row0, q->d_w, d_seg_off, chunk, q->n, n_seg, d_cols, d_ncols, REEVAL_CAP, \
                        (double *)ctx->ws_seg_score.p, (uint32_t *)ctx->ws_seg_miss.p, ld)
             if (skip) {

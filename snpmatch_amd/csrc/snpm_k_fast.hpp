@@ -62,6 +62,14 @@ __device__ __forceinline__ void load_row(const int8_t *p, uint32_t (&x)[1])
 //   Partial sums are written out and restarted every EPOCH_TILES tiles of a part (epoch e of part p goes
 //   to slot e*P + p): accumulation chains stay short (tight rounding bound, u16 counters never overflow).
 //   out_score [n_epochs*P, ld] fp64, out_miss [n_epochs*P, ld] u32 (ld = pitch).
+//   n_acc = valid bytes of a row.  A cache line that holds only padding (bytes from roundup(n_acc, 128) on: 0xFF) is never
+//   fetched: its lanes load the dword of the last valid byte instead -- a line the wave fetches anyway -- and take 0xFF for
+//   what they read, so the pad columns keep the sums they always had.  "Take 0xFF" costs nothing per row: the bytes of a row
+//   are used twice, for the LUT index (code & 3) * 8 | row offset, into which a pad lane ORs 0x18 (code 3 = 0xFF & 3) once per
+//   row group, and for the byte counters of missing calls, which a pad lane sets to the tile's row count at the tile's flush.
+//   Only the PAD instantiations do this; the host takes them for panels that have such a line (fast_has_pad_line) and the
+//   others compile to the code they always were.  (With PAD the pad columns' sums no longer depend on what the pad bytes of
+//   the panel hold: every writer of the library fills them with 0xFF, a caller writing through the raw device pointer may not.)
 // launch bound: <= 512 threads and (for the 4 B/lane layout) >= 6 waves per SIMD, i.e. <= 80 VGPRs: the
 // kernel is latency-bound and 5-wave blocks only fit 4 per CU with 6 wave slots per SIMD (measured:
 // 79-82 % of HBM peak at 80 VGPRs vs 67-70 % at 88; asking for 7 waves changes nothing -- the kernel already
@@ -70,11 +78,11 @@ __device__ __forceinline__ void load_row(const int8_t *p, uint32_t (&x)[1])
 // [part_desc[3p], part_desc[3p+1]) of the (concatenated) matched list -- never more than EPOCH_TILES tiles, all inside
 // one segment -- and writes its partial sums to slot part_desc[3p+2]; k_reduce_seg adds the slots of a segment in
 // order.  Without SEG the arguments part_desc is unused and the code is the tile-interleaved pass described above.
-template <bool SKIP, bool GATHER, bool SEG = false, int TR = TILE_ROWS>
+template <bool SKIP, bool GATHER, bool SEG = false, int TR = TILE_ROWS, bool PAD = false>
 __global__ void __launch_bounds__(WAVE *MAX_WAVES_PER_BLOCK, SNPM_FAST_MIN_WAVES)
 k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__ row_idx, int64_t row0, int64_t n,
        const double *__restrict__ lut, double *__restrict__ out_score, uint32_t *__restrict__ out_miss, int64_t ld,
-       const int64_t *__restrict__ part_desc = nullptr, int tile_rows_rt = 0)
+       int64_t n_acc, const int64_t *__restrict__ part_desc = nullptr, int tile_rows_rt = 0)
 {
     // BPL = bytes (= accessions = accumulators) per lane and row: one dword.  8 and 16 B per lane streamed at 4.4 and 5.3 TB/s
     // against 6.5 TB/s (10k x 6.25M panel, round 1) and were removed; packed panels have their own kernels below
@@ -96,6 +104,9 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
     // a lane works when its bytes lie inside the row (pitch is a multiple of 256 B) and its accessions inside the result
     // arrays (ld); blocks may carry spare waves
     const bool lane_on = byte0 < pitch && col0 < ld;
+    // a lane whose cache line holds only padding
+    const bool pad_lane = PAD && lane_on && byte0 >= (n_acc + 127) / 128 * 128;
+    const uint32_t pad18 = pad_lane ? 0x18181818u : 0u;
     const int64_t p = SEG ? (int64_t)blockIdx.y + (int64_t)gridDim.y * blockIdx.z : (int64_t)blockIdx.y;
     if (SEG && p >= n) return;             // SEG: n is the number of parts (grid.y * grid.z may exceed it)
     // tiles of this block: T = T0, T0 + TS, ... < n_tiles_total; tile T = rows [rbase + T * TR, ...) up to rend
@@ -119,7 +130,7 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
 
     // address = wave-uniform row base (scalar registers) + 32-bit lane offset: global_load saddr form,
     // no per-lane 64-bit address arithmetic
-    const uint32_t lane_off = lane_on ? (uint32_t)byte0 : 0u;
+    const uint32_t lane_off = !lane_on ? 0u : (pad_lane ? (uint32_t)((n_acc - 1) & ~(int64_t)3) : (uint32_t)byte0);
     auto row_ptr = [&](int64_t rr) -> const int8_t * {
         const int64_t prow = GATHER ? row_idx[rr] : (row0 + rr);
         const int8_t *rowbase = db + prow * pitch;                 // wave-uniform: scalar registers
@@ -202,7 +213,7 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
         const uint32_t goff_ = (uint32_t)(GI) * (uint32_t)(G * LUT_ROW_BYTES);              \
         const uint32_t gbase_ = lds_base + (goff_ & ~255u);                                 \
         const uint32_t roff_ = goff_ & 255u;                                                \
-        const uint32_t roff4_ = roff_ * 0x01010101u;                                        \
+        const uint32_t roff4_ = (roff_ * 0x01010101u) | pad18;                              \
         SCORE_ROW(0, (X)[0], gbase_, roff4_, roff_);                                        \
         SCORE_ROW(1, (X)[1], gbase_, roff4_, roff_);                                        \
         if constexpr (G > 2) {                                                              \
@@ -239,12 +250,13 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
                 uint32_t x[NDW];
                 load_row(row_ptr(tr0 + r), x);
                 const uint32_t group_base = lds_base + (uint32_t)(r >> 3) * 256u;
-                const uint32_t roff4 = (uint32_t)(r & 7) * 0x20202020u;        // (r & 7) * 32 in every byte
+                const uint32_t roff4 = ((uint32_t)(r & 7) * 0x20202020u) | pad18;        // (r & 7) * 32 in every byte
                 SCORE_ROW(0, x, group_base, roff4, (uint32_t)(r & 7) * 32u);
             }
             // flush packed u8 counters (<= TR <= 255 per byte) into packed u16 pairs
 #pragma unroll
             for (int k = 0; k < NDW; ++k) {
+                if (pad_lane) miss8[k] = (uint32_t)rows * 0x01010101u;    // every call of a pad byte is missing
                 miss16[2 * k + 0] += miss8[k] & 0x00ff00ffu;          // bytes 0 and 2
                 miss16[2 * k + 1] += (miss8[k] >> 8) & 0x00ff00ffu;   // bytes 1 and 3
                 miss8[k] = 0;
