@@ -434,7 +434,9 @@ int snpm_profile_reset(snpm_ctx *ctx);
    snpm_panel_ld_band, one launch each per slab), "win_planes" / "win_count" (the two kernels of snpm_panel_window_counts, one
    launch each per slab), "f1x_count" (the count kernel of snpm_panel_f1_counts, one launch per slab; its planes are a
    "win_planes" launch per slab), "par_count" (the count kernel of snpm_panel_parent_counts, one launch per slab of whole windows
-   and 65535 groups; its planes are a "win_planes" launch per slab).  Synchronises the stream. */
+   and 65535 groups; its planes are a "win_planes" launch per slab), "sim_noise" / "sim_count" (the two kernels of
+   snpm_panel_sim_counts, one launch each per slab, "sim_noise" only with err_thr > 0; its planes are a "win_planes" launch per
+   slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -674,6 +676,41 @@ int snpm_panel_f1_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, 
 int snpm_panel_parent_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                              const uint8_t *sample_class, const int64_t *win_off, int64_t n_win, int32_t min_win_sites, int32_t *score,
                              int32_t *n_tot, int32_t *w_first, int32_t *w_het);
+
+/* ---------------------------------------------------------------- power */
+/* The sample SIMULATED from every listed accession column -- its calls at the selected rows with call errors injected -- scored
+   against every listed accession column, per group of selected rows: what simulateSNPs followed by inbred answers for one accession
+   and one marker count at a time (core/simulate.py:26-53, core/snpmatch.py:74-117 of the reference), for all accessions and a whole
+   ladder of marker counts, on the RESIDENT panel (int8 or packed), as one call.  Host pointers in and out.
+     cols [ncols]     accession columns, any order, repeats allowed; NULL = all accessions (ncols must then be the panel's count)
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows)
+     grp_off [n_grp + 1]   offsets into the SELECTED rows: starts at 0, never decreases, ends at n_rows; group g holds the selected
+                      rows [grp_off[g], grp_off[g + 1]).  Empty groups are allowed anywhere; a group may start and end anywhere
+     err_thr          0 .. 2^32: the call error rate times 2^32
+     seed             of the counter-based hash
+   On canonical DB codes (0, 1, 2, 3 = an int8 panel's "other" code, missing), with a the POSITION of a column in the column list and
+   k the POSITION of a row in the selected rows: the sample of a has a call at k when a's code there is 0, 1 or 2.  Its class is that
+   code unless (h >> 32) < err_thr; then it is ((h & 0xFFFFFFFF) * 3) >> 32 (which may be the code itself), with
+     h = mix(mix(seed + 0x9E3779B97F4A7C15 * (a + 1)) ^ k),   mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+                                                                       z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^ z >> 31
+   in 64-bit unsigned arithmetic (two rounds of the splitmix64 finaliser).  A column listed twice gives two independent samples.
+     ninfo [n_grp][ncols][ncols]   ninfo[g][a][b] = rows of g where sample a has a call and b's code is not missing (code 3 counts)
+     score [n_grp][ncols][ncols]   score[g][a][b] = rows of g where b's code is sample a's class
+   Exact int32 counts; the matrices are NOT symmetric (a is the sample, b the DB column).  With the one-hot weights of the sample
+   they are the reference's NumInfoSites / ScoreList.  The counts of disjoint groups add: the cumulative sum over g of a ladder of
+   nested marker sets drawn by the host gives every level from one call.
+   The row axis is processed in slabs whose SEVEN bit-planes (7 bits per call: four of the DB, three of the samples) fit a workspace
+   budget (512 MiB; SNPM_SIM_WS_MB, read by snpm_init); up to three launches per slab, the counts accumulate on the device, and the
+   hash is keyed by the position in the selection, so the result does not depend on the budget.
+   Limits: ncols <= SNPM_SIM_MAX_ACCESSIONS, n_rows < 2^31, 1 <= n_grp <= 64, n_grp * ncols * ncols < 2^31.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, the
+   limits, grp_off sound, err_thr <= 2^32, non-NULL outputs when ncols > 0 -- these before the panel handle is looked at, the
+   message of a NULL panel is in snpm_last_error(NULL) -- then every column and row inside the panel, then ncols == the panel's
+   accession count when cols is NULL.  ncols == 0 writes nothing; n_rows == 0 writes zeros without a launch.  Uploads into the panel
+   that are still in flight are waited for on the device. */
+#define SNPM_SIM_MAX_ACCESSIONS 11552
+int snpm_panel_sim_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                          const int64_t *grp_off, int64_t n_grp, uint64_t err_thr, uint64_t seed, int32_t *score, int32_t *ninfo);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

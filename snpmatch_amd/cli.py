@@ -11,7 +11,9 @@ either) counts the alleles of every DB row per population on the device and writ
 neighbouring DB rows inside a band on the device and prunes the rows by it; ``windows`` (not in the reference as a command) counts, per genome window, the
 heterozygosity of every accession and the mismatch of listed pairs of accessions on the device; ``f1search`` (not in the reference) scores
 the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles; ``parentsearch`` (not in the reference)
-scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third.  The other reference subcommands (parser, makedb, simulate) are outside the accelerated
+scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
+the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
+counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses.  The other reference subcommands (parser, makedb) are outside the accelerated
 path.
 """
 import argparse
@@ -149,6 +151,24 @@ def snpmatch_parentsearch(args):
     if args['accFile']:
         check_file(args['accFile'])
     parentsearch.potatoParentSearch(args)
+
+
+def snpmatch_simulate(args):
+    from .core import simulate
+    check_file(args['hdf5File'])
+    if not args['AccID']:
+        die("accession not specified: -a 6091 (or -a 6091x6191 with --f1)")
+    if args['numSNPs'] is None or args['numSNPs'] < 0:
+        die("number of SNPs not specified: -n 1000")
+    simulate.potatoSimulate(args)
+
+
+def snpmatch_power(args):
+    from .core import power
+    check_file(args['hdf5File'])
+    if args['accFile']:
+        check_file(args['accFile'])
+    power.potatoPower(args)
 
 
 def makedb_native(args):
@@ -337,6 +357,37 @@ def get_options(description, version_message):
     par.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     par.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.parentsearch.json, <prefix>.parentsearch.npz and <prefix>.parentsearch.windows.tsv")
     par.set_defaults(func=snpmatch_parentsearch)
+
+    # the reference's command, host only: the same draws as the reference under one seed
+    sim = sub.add_parser('simulate', help="Given SNP database, check the genotyping efficiency randomly selecting 'n' number of SNPs")
+    sim.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File", help="Path to SNP matrix (as for inbred)")
+    sim.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    sim.add_argument("-a", "--ecotype_id", dest="AccID", help="Ecotype ID you want draw the SNPs")
+    sim.add_argument("-n", "--number_of_snps", dest="numSNPs", help="number of SNPs to draw in random to genotype the sample", type=int)
+    sim.add_argument("-p", "--error_rate", dest="err_rate", default=0.001, type=float,
+                     help="error rate while matching the SNPs, error rate of 0 gives perfect match to the accession")
+    sim.add_argument("--f1", action="store_true", dest="simF1", default=False, help="Simulate SNPs for an F1, give parents as 1061x1062 in argument '-a'")
+    sim.add_argument("--het_frac", default=1, type=float, dest="rm_het",
+                     help="for F1s: the probability that a segregating site stays heterozygous; the rest become homozygous ref or alt, half each")
+    sim.add_argument("--seed", dest="seed", default=None, type=int, help="np.random.seed before the draws (not in the reference): the same sample again")
+    sim.add_argument("-o", "--output", dest="outFile", help="Output BED file: chromosome, position, genotype")
+    sim.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    sim.set_defaults(func=snpmatch_simulate)
+
+    # not in the reference (simulate + inbred, one accession and one n at a time): every accession simulated and scored against every accession
+    pw = sub.add_parser('power', help="identifiability of every accession of the database: with n random SNPs and a call error rate, whom does inbred identify uniquely, whom does it confuse")
+    pw.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    pw.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    pw.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    pw.add_argument("--bed", dest="bed", default=None, help="draw the markers from the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
+    pw.add_argument("-n", "--number_of_snps", dest="levels", required=True, help="the ladder of marker counts, increasing: 100,1000,10000 (at most 64 levels)")
+    pw.add_argument("-p", "--error_rate", dest="err_rate", default=0.001, type=float, help="probability that a call of the simulated sample is redrawn from ref / alt / het (default 0.001)")
+    pw.add_argument("--trials", dest="trials", default=3, type=int, help="marker ladders drawn, one device call each (default 3)")
+    pw.add_argument("--seed", dest="seed", default=1, type=int, help="seed of the ladders and of the injected errors (default 1)")
+    pw.add_argument("--lr_thres", dest="lr_thres", default=3.841, type=float, help="an accession is ambiguous with the top hit below this likelihood ratio (default 3.841, as inbred)")
+    pw.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    pw.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.power.tsv, <prefix>.power.json and <prefix>.power.npz")
+    pw.set_defaults(func=snpmatch_power)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -434,6 +434,14 @@ class Genotype(object):
         return engine.parent_counts(_resident_panel(self, "the parent search needs"), sample_class, win_off, min_win_sites, filter_acc_ix,
                                     _rows_or_range(filter_snp_ix))
 
+    def sim_counts(self, grp_off, err_rate, seed, filter_acc_ix=None, filter_snp_ix=None):
+        """(score, ninfo) int32 [n_grp, n, n] of the sample simulated from every listed accession (its calls at the listed DB rows,
+        errors at ``err_rate`` injected under ``seed``) against every listed accession, per group of the listed rows as ``grp_off``
+        cuts them, counted on the resident panel (``engine.sim_counts``).  Row a is the sample, column b the DB accession.  None = all
+        accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        return engine.sim_counts(_resident_panel(self, "the power study needs"), grp_off, err_rate, seed, filter_acc_ix, _rows_or_range(filter_snp_ix))
+
     # ------------------------------------------------------------------ site statistics
     def site_counts(self, filter_acc_ix=None, filter_snps_ix=None):
         """int32 [G, n, 4] -- c0, c1, c2 (listed accessions with code 0 / 1 / 2) and ninfo (listed accessions with a call) of every

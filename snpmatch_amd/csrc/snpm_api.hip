@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count"};
 
 struct Buf {
     void *p = nullptr;
@@ -68,6 +68,8 @@ struct Buf {
     X(ws_f1x_planes) X(ws_f1x_masks) X(ws_f1x_cols) X(ws_f1x_out)                                                                 \
     /* snpm_panel_parent_counts (snpm_api_par.hpp): bit-planes [4][cols_pad][W] of a slab; group table; step offsets; segments; column list; score | n_tot | w_first | w_het */ \
     X(ws_par_planes) X(ws_par_groups) X(ws_par_steps) X(ws_par_segs) X(ws_par_cols) X(ws_par_out)                                 \
+    /* snpm_panel_sim_counts (snpm_api_sim.hpp): bit-planes [4 + 3][cols_pad][W] of a slab; grp_off; column list; score | ninfo */ \
+    X(ws_sim_planes) X(ws_sim_grp) X(ws_sim_cols) X(ws_sim_out)                                                                   \
     /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
     /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
     X(ws_rows)                                                                                                                    \
@@ -118,6 +120,7 @@ struct snpm_ctx {
     size_t win_ws_bytes = size_t(256) << 20;    // SNPM_WIN_WS_MB: planes and cells of one row slab of snpm_panel_window_counts
     size_t f1x_ws_bytes = size_t(512) << 20;    // SNPM_F1X_WS_MB: bit-planes of one row slab of snpm_panel_f1_counts
     size_t par_ws_bytes = size_t(512) << 20;    // SNPM_PAR_WS_MB: bit-planes of one slab of whole windows of snpm_panel_parent_counts
+    size_t sim_ws_bytes = size_t(512) << 20;    // SNPM_SIM_WS_MB: the seven bit-planes of one row slab of snpm_panel_sim_counts
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -510,6 +513,7 @@ try {
     if (const char *s = getenv("SNPM_WIN_WS_MB")) ctx->win_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_F1X_WS_MB")) ctx->f1x_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_PAR_WS_MB")) ctx->par_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_SIM_WS_MB")) ctx->sim_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -663,6 +667,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_f1x.hpp"
 
 #include "snpm_api_par.hpp"
+
+#include "snpm_api_sim.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

@@ -835,6 +835,49 @@ def parent_counts(panel, sample_class, win_off, min_win_sites=1, cols=None, rows
     return score, n_tot, w_first, w_het
 
 
+SIM_MAX_ACCESSIONS = 11552     # SNPM_SIM_MAX_ACCESSIONS: columns of one ``sim_counts`` call
+SIM_MAX_GROUPS = 64            # groups of one ``sim_counts`` call
+
+
+def sim_err_threshold(err_rate):
+    """the library's ``err_thr`` of an error rate in [0, 1]: floor(err_rate * 2^32)"""
+    err_rate = float(err_rate)
+    if not 0.0 <= err_rate <= 1.0:
+        raise ValueError("err_rate must lie in 0 .. 1: got %r" % (err_rate,))
+    return int(np.floor(err_rate * 4294967296.0))
+
+
+def sim_counts(panel, grp_off, err_rate, seed, cols=None, rows=None):
+    """The sample SIMULATED from every accession column of a resident panel -- its calls at the selected rows, each replaced with
+    probability ``err_rate`` by a class drawn from 0 / 1 / 2 by a counter-based hash of (``seed``, position of the column in the list,
+    position of the row in the selection) -- scored against every accession column, per group of selected rows, in one device call
+    (``snpm_panel_sim_counts``).  ``grp_off`` [n_grp + 1]: offsets into the SELECTED rows (starts at 0, never decreases, ends at the
+    row count; empty groups allowed; at most 64 groups); ``cols`` / ``rows`` as for ``kinship_counts``.  Returns ``(score, ninfo)``,
+    int32 [n_grp, n_cols, n_cols], NOT symmetric: ``ninfo[g, a, b]`` rows of group g where sample a has a call and column b's is not
+    missing, ``score[g, a, b]`` rows where column b's code is sample a's class -- the reference's NumInfoSites / ScoreList of that
+    sample against b.  Group (accession-sharded) and streamed panels are refused."""
+    _need_resident_panel(panel, "sim_counts")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    grp_off = np.ascontiguousarray(grp_off, dtype=np.int64).reshape(-1)
+    assert len(grp_off) >= 1, "grp_off holds n_grp + 1 entries"
+    n_grp = len(grp_off) - 1
+    err_thr = sim_err_threshold(err_rate)
+    seed = int(seed) % (1 << 64)
+    if ncols > SIM_MAX_ACCESSIONS:          # the library's limits, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_SIM_MAX_ACCESSIONS)" % (ncols, SIM_MAX_ACCESSIONS))
+    if not 1 <= n_grp <= SIM_MAX_GROUPS or n_grp * ncols * ncols >= 1 << 31:
+        check(ctx.lib.snpm_panel_sim_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(grp_off), n_grp, err_thr, seed, None, None), ctx.h)
+    score, ninfo = (np.empty((n_grp, ncols, ncols), dtype=np.int32) for _ in range(2))
+    check(ctx.lib.snpm_panel_sim_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(grp_off), n_grp, err_thr, seed, ptr(score), ptr(ninfo)), ctx.h)
+    return score, ninfo
+
+
 SITE_MAX_GROUPS = 32           # SNPM_SITE_MAX_GROUPS: groups of one ``snpm_panel_site_counts`` call
 
 
