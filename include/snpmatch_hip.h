@@ -436,7 +436,8 @@ int snpm_profile_reset(snpm_ctx *ctx);
    "win_planes" launch per slab), "par_count" (the count kernel of snpm_panel_parent_counts, one launch per slab of whole windows
    and 65535 groups; its planes are a "win_planes" launch per slab), "sim_noise" / "sim_count" (the two kernels of
    snpm_panel_sim_counts, one launch each per slab, "sim_noise" only with err_thr > 0; its planes are a "win_planes" launch per
-   slab).  Synchronises the stream. */
+   slab), "mos_fwd" / "mos_back" (the two kernels of snpm_panel_mosaic, one launch each per slab of whole chains and group of
+   samples; its planes are a "win_planes" launch per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -711,6 +712,45 @@ int snpm_panel_parent_counts(snpm_panel *panel, const int32_t *cols, int64_t nco
 #define SNPM_SIM_MAX_ACCESSIONS 11552
 int snpm_panel_sim_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                           const int64_t *grp_off, int64_t n_grp, uint64_t err_thr, uint64_t seed, int32_t *score, int32_t *ninfo);
+
+/* ---------------------------------------------------------------- mosaic */
+/* A sample as a MOSAIC of the listed accession columns: the copying-model Viterbi (Li & Stephens with a uniform switch cost) whose
+   states are all the listed columns, with integer costs, for every (chain, sample) in one call on the RESIDENT panel (int8 or
+   packed).  The reference has nothing like it: inbred assumes one accession, cross two.  Host pointers in and out.
+     cols [ncols]     accession columns, any order, repeats allowed; NULL = all accessions (ncols must then be the panel's count)
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows)
+     chain_off [n_chain + 1]  offsets into the SELECTED rows: starts at 0, never decreases, ends at n_rows.  A chain (a chromosome)
+                      is the selected rows [chain_off[c], chain_off[c + 1]); empty chains are allowed anywhere
+     sample_class [n_samples][n_rows]  per sample and selected row 0 ref, 1 alt, 2 het, 0xFF no class (as snpm_panel_f1_counts)
+     cost [3][4]      uint8, every entry 0 .. 15: cost[sample class][canonical DB code 0, 1, 2, 3]; 3 is an int8 panel's "other" code
+     switch_cost      S, 1 .. 2^20
+   With a the POSITION of a column in the column list and k the POSITION of a row in the selected rows:
+     e(a, k) = cost[class of the sample at k][code of a at k]; 0 when the sample has no class at k or the call of a is missing
+               (a negative int8, the 2-bit value 3); an int8 panel's code 3 is NOT missing
+   and per (sample, non-empty chain [c0, c1)):
+     V(a, c0) = e(a, c0);  for k > c0:  B = min_a V(a, k - 1),  j(k - 1) = the LOWEST a that attains B,
+                                        sw(a, k) = V(a, k - 1) > B + S  (strict: a tie stays),
+                                        V(a, k) = min(V(a, k - 1), B + S) + e(a, k)
+     chain_cost = min_a V(a, c1 - 1);  state[c1 - 1] = the LOWEST a that attains it;  state[k - 1] = sw(state[k], k) ? j(k - 1) : state[k]
+   A column listed twice is two states; the tie rules decide between them.
+     state [n_samples][n_rows]            int32 positions in the column list
+     chain_cost [n_samples][n_chain]      int32, 0 for an empty chain
+     col_cost [n_samples][n_chain][ncols] int32 sum over the chain of e(a, k): the cost of never switching; NULL to skip
+   The chain axis is processed in slabs of WHOLE chains whose bit-planes fit a workspace budget (512 MiB; SNPM_MOS_WS_MB, read by
+   snpm_init) beside the backpointer words of one sample -- a chain larger than the budget is a slab of its own -- and the samples in
+   groups of as many as fit; a chain is always computed whole by one block, so the result does not depend on the budget.
+   Limits: ncols <= SNPM_MOS_MAX_ACCESSIONS, n_rows < 2^31, n_chain <= SNPM_MOS_MAX_CHAINS, 15 * (longest chain) + S < 2^31.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, the
+   limits, chain_off sound, n_samples >= 1 when there are rows and columns, cost entries <= 15, S in range, the class bytes,
+   non-NULL state / chain_cost when they would be written -- these before the panel handle is looked at, the message of a NULL
+   panel is in snpm_last_error(NULL) -- then every column and row inside the panel, then ncols == the panel's accession count when
+   cols is NULL.  ncols == 0 or n_samples == 0 writes nothing; n_rows == 0 writes zero costs without a launch.  Uploads into the
+   panel that are still in flight are waited for on the device. */
+#define SNPM_MOS_MAX_ACCESSIONS 12288
+#define SNPM_MOS_MAX_CHAINS 1048576
+int snpm_panel_mosaic(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                      const int64_t *chain_off, int64_t n_chain, const uint8_t *sample_class, int64_t n_samples, const uint8_t *cost,
+                      int32_t switch_cost, int32_t *state, int32_t *chain_cost, int32_t *col_cost);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

@@ -13,7 +13,8 @@ heterozygosity of every accession and the mismatch of listed pairs of accessions
 the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles; ``parentsearch`` (not in the reference)
 scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
 the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
-counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses.  The other reference subcommands (parser, makedb) are outside the accelerated
+counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses; ``mosaic`` (not in the reference) paints a sample of more than two
+sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state.  The other reference subcommands (parser, makedb) are outside the accelerated
 path.
 """
 import argparse
@@ -169,6 +170,15 @@ def snpmatch_power(args):
     if args['accFile']:
         check_file(args['accFile'])
     power.potatoPower(args)
+
+
+def snpmatch_mosaic(args):
+    from .core import mosaic
+    check_file(args['inFile'])
+    check_file(args['hdf5File'])
+    if args['accFile']:
+        check_file(args['accFile'])
+    mosaic.potatoMosaic(args)
 
 
 def makedb_native(args):
@@ -388,6 +398,20 @@ def get_options(description, version_message):
     pw.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     pw.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.power.tsv, <prefix>.power.json and <prefix>.power.npz")
     pw.set_defaults(func=snpmatch_power)
+
+    # not in the reference: a sample of more than two sources (MAGIC lines, multi-parent RILs, admixed samples) painted accession by accession
+    mos = sub.add_parser('mosaic', help="paint every sample of the input as a mosaic of the accessions of the database: which accession it copies at every matched SNP (copying-model Viterbi with a uniform switch cost)")
+    mos.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF/BED file of the sample; a multi-sample VCF is painted as a batch on its shared records")
+    mos.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    mos.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    mos.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession (founder) name per line (default: all accessions)")
+    mos.add_argument("--switch_cost", dest="switch_cost", default=40, type=int, help="cost of a change of accession, 1 .. 1048576 (default 40)")
+    mos.add_argument("--mismatch", dest="mismatch", default=2, type=int, help="cost of a homozygous call against the other homozygous call, or against the DB's 'other' code, 0 .. 15 (default 2)")
+    mos.add_argument("--het_cost", dest="het_cost", default=1, type=int, help="cost of a heterozygous call against a homozygous one, either way, 0 .. 15 (default 1)")
+    mos.add_argument("--min_seg_sites", dest="min_seg_sites", default=20, type=int, help="segments of fewer sites are flagged in the segment table (default 20)")
+    mos.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    mos.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.mosaic.segments.tsv, <prefix>.mosaic.json and <prefix>.mosaic.npz")
+    mos.set_defaults(func=snpmatch_mosaic)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

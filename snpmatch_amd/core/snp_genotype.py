@@ -442,6 +442,15 @@ class Genotype(object):
         from .. import engine
         return engine.sim_counts(_resident_panel(self, "the power study needs"), grp_off, err_rate, seed, filter_acc_ix, _rows_or_range(filter_snp_ix))
 
+    def mosaic(self, classes, chain_off, cost, switch_cost, filter_acc_ix=None, filter_snp_ix=None, want_col_cost=False):
+        """(state, chain_cost, col_cost) of the samples painted as mosaics of the listed accessions over the listed DB rows, which
+        ``chain_off`` cuts into chains (``engine.mosaic``: the copying-model Viterbi on the resident panel).  ``classes``: uint8
+        [n_samples, n_rows], one class per sample and listed row (0 ref, 1 alt, 2 het, 0xFF none).  None = all accessions / all
+        rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        return engine.mosaic(_resident_panel(self, "the mosaic needs"), classes, chain_off, cost, switch_cost, filter_acc_ix, _rows_or_range(filter_snp_ix),
+                             want_col_cost)
+
     # ------------------------------------------------------------------ site statistics
     def site_counts(self, filter_acc_ix=None, filter_snps_ix=None):
         """int32 [G, n, 4] -- c0, c1, c2 (listed accessions with code 0 / 1 / 2) and ninfo (listed accessions with a call) of every

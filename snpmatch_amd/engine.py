@@ -878,6 +878,53 @@ def sim_counts(panel, grp_off, err_rate, seed, cols=None, rows=None):
     return score, ninfo
 
 
+MOS_MAX_ACCESSIONS = 12288     # SNPM_MOS_MAX_ACCESSIONS: columns (states) of one ``mosaic`` call
+MOS_SWITCH_MAX = 1 << 20       # the largest switch cost
+
+
+def mosaic(panel, classes, chain_off, cost, switch_cost, cols=None, rows=None, want_col_cost=False):
+    """Samples as MOSAICS of the accession columns of a resident panel: the copying-model Viterbi with a uniform switch cost and
+    integer costs, the states being all the listed columns, for every (chain, sample) in one device call (``snpm_panel_mosaic``;
+    include/snpmatch_hip.h states the model).  ``classes``: uint8 [n_samples, n_rows] (or [n_rows], one sample), per selected row
+    0 ref, 1 alt, 2 het, 0xFF none; ``chain_off`` [n_chain + 1]: offsets into the SELECTED rows (starts at 0, never decreases, ends
+    at the row count; a chain is a chromosome; empty chains allowed); ``cost`` [3, 4]: entries 0 .. 15, indexed [sample class][DB
+    code 0, 1, 2, 3]; ``switch_cost`` 1 .. 2^20; ``cols`` / ``rows`` as for ``kinship_counts``.  Returns ``(state, chain_cost,
+    col_cost)``: int32 [n_samples, n_rows] positions in the column list, int32 [n_samples, n_chain], and int32 [n_samples, n_chain,
+    n_cols] -- the cost of never switching -- or None without ``want_col_cost``.  Group (accession-sharded) and streamed panels are
+    refused."""
+    _need_resident_panel(panel, "mosaic")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    classes = np.ascontiguousarray(classes, dtype=np.uint8)
+    if classes.ndim == 1:
+        classes = classes.reshape(1, -1)
+    assert classes.ndim == 2 and classes.shape[1] == n_rows, "one class per sample and selected row: classes %s, %d rows" % (classes.shape, n_rows)
+    n_samples = classes.shape[0]
+    chain_off = np.ascontiguousarray(chain_off, dtype=np.int64).reshape(-1)
+    assert len(chain_off) >= 1, "chain_off holds n_chain + 1 entries"
+    n_chain = len(chain_off) - 1
+    cost = np.ascontiguousarray(cost)
+    assert cost.shape == (3, 4), "cost is [3, 4]: [sample class][DB code]"
+    assert cost.dtype.kind in "iu" and cost.min() >= 0 and cost.max() <= 255, "cost holds small non-negative integers"
+    cost = cost.astype(np.uint8)
+    switch_cost = int(switch_cost)
+    if not -2 ** 31 <= switch_cost < 2 ** 31:
+        raise AssertionError("switch_cost must be 1 .. 2^20")
+    if ncols > MOS_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_MOS_MAX_ACCESSIONS)" % (ncols, MOS_MAX_ACCESSIONS))
+    state = np.empty((n_samples, n_rows), dtype=np.int32)
+    chain_cost = np.empty((n_samples, n_chain), dtype=np.int32)
+    col_cost = np.empty((n_samples, n_chain, ncols), dtype=np.int32) if want_col_cost else None
+    check(ctx.lib.snpm_panel_mosaic(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(chain_off), n_chain, ptr(classes), n_samples,
+                                    ptr(cost), switch_cost, ptr(state), ptr(chain_cost), ptr(col_cost)), ctx.h)
+    return state, chain_cost, col_cost
+
+
 SITE_MAX_GROUPS = 32           # SNPM_SITE_MAX_GROUPS: groups of one ``snpm_panel_site_counts`` call
 
 
