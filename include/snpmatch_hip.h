@@ -437,7 +437,9 @@ int snpm_profile_reset(snpm_ctx *ctx);
    and 65535 groups; its planes are a "win_planes" launch per slab), "sim_noise" / "sim_count" (the two kernels of
    snpm_panel_sim_counts, one launch each per slab, "sim_noise" only with err_thr > 0; its planes are a "win_planes" launch per
    slab), "mos_fwd" / "mos_back" (the two kernels of snpm_panel_mosaic, one launch each per slab of whole chains and group of
-   samples; its planes are a "win_planes" launch per slab).  Synchronises the stream. */
+   samples; its planes are a "win_planes" launch per slab), "ibd_count" / "ibd_runs" (the two kernels of snpm_panel_ibd_counts:
+   "ibd_count" one launch per slab of whole windows and 65535 groups, "ibd_runs" one launch per call; its planes are a "win_planes"
+   launch per slab).  Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -751,6 +753,44 @@ int snpm_panel_sim_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols,
 int snpm_panel_mosaic(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                       const int64_t *chain_off, int64_t n_chain, const uint8_t *sample_class, int64_t n_samples, const uint8_t *cost,
                       int32_t switch_cost, int32_t *state, int32_t *chain_cost, int32_t *col_cost);
+
+/* ---------------------------------------------------------------- ibd */
+/* For EVERY pair of listed accession columns, WHERE along the genome the two are identical -- shared haplotype segments, identity by
+   descent -- on the RESIDENT panel (int8 or packed), as one call: snpm_panel_kinship_counts counts every pair over all rows,
+   snpm_panel_window_counts looks along the genome for listed pairs only.  Host pointers in and out.
+     cols, row_idx / row0 / n_rows, win_off / n_win   as for snpm_panel_parent_counts (without the sample)
+     min_win_sites     a window is USED for a cell only with this many rows or more (>= 1)
+     max_diff_ppm      0 .. 1 000 000: the share of differing rows, in parts per million, up to which a used window is SHARED
+     min_run           a run is REPORTED with this many shared windows or more (>= 1)
+   Per cell (a, b) -- positions in the column list -- and window, on canonical codes: n = rows where both calls are homozygous (code
+   0 or 1), d = rows among them where the two codes differ (hom_same + hom_diff and hom_diff of snpm_panel_window_counts).  Hets, an
+   int8 panel's code 3 and missing calls count nowhere.  The window is used iff n >= min_win_sites, shared iff used and
+   d * 1 000 000 <= max_diff_ppm * n (64-bit integers), a break iff used and not shared.  The windows of the call are scanned in
+   order (a caller hands over one chromosome per call): a run is a maximal set of shared windows with no break between two
+   consecutive members; unused windows neither break a run nor count in it; its length is its number of shared windows.
+     w_used, w_shared  [ncols, ncols]  windows used / shared
+     n_shared, d_shared [ncols, ncols] sums of n / d over the shared windows
+     run_max           [ncols, ncols]  the longest run (0: none), whatever min_run
+     n_runs, w_in_runs [ncols, ncols]  the reported runs and the shared windows inside them
+     used_bits, shared_bits [ncols, ncols, wwords]  uint32, wwords = ceil(n_win / 32): window w is bit w % 32 of word w / 32, bits at
+                       and above n_win are zero; either pointer may be NULL (that bitset is not copied back)
+   Exact int32, full and symmetric; on the diagonal d = 0, so every used window is shared.
+   The windows are processed in slabs of WHOLE windows whose bit-planes (4 bits per call) fit a workspace budget (512 MiB;
+   SNPM_IBD_WS_MB, read by snpm_init; a window larger than the budget is a slab of its own); every (cell, window) is evaluated
+   whole by one block, so the result does not depend on the budget.  The two bitsets live on the device for the whole call (the
+   runs are made from them) and must fit SNPM_IBD_BITS_MB (2048 MiB, read by snpm_init; 1135 accessions x 399 windows take 134 MB):
+   a call whose bitsets do not fit is refused with SNPM_ERR_BADARG, the message states the bytes needed and names the variable.
+   Limits: ncols <= SNPM_F1X_MAX_ACCESSIONS, n_rows < 2^31.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size,
+   n_win >= 0, min_win_sites >= 1, max_diff_ppm in range, min_run >= 1, the limits, win_off sound, the seven matrices non-NULL when
+   ncols > 0 -- these before the panel handle is looked at, the message of a NULL panel is in snpm_last_error(NULL) -- then every
+   column and row inside the panel, then ncols == the panel's accession count when cols is NULL, then the bitset budget.
+   ncols == 0 writes nothing; n_rows == 0 or n_win == 0 writes zeros without a launch.  Uploads into the panel that are still in
+   flight are waited for on the device. */
+int snpm_panel_ibd_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                          const int64_t *win_off, int64_t n_win, int32_t min_win_sites, int32_t max_diff_ppm, int32_t min_run,
+                          int32_t *w_used, int32_t *w_shared, int32_t *n_shared, int32_t *d_shared,
+                          int32_t *run_max, int32_t *n_runs, int32_t *w_in_runs, uint32_t *used_bits, uint32_t *shared_bits);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

@@ -58,6 +58,7 @@ SYMBOLS = [
     "snpm_panel_parent_counts",
     "snpm_panel_sim_counts",
     "snpm_panel_mosaic",
+    "snpm_panel_ibd_counts",
 ]
 
 _lib = None
@@ -256,6 +257,7 @@ def load():
     lib.snpm_panel_window_counts.argtypes = [p, p, i64, p, p, i64, p, i64, i64, p, i64, p, p]
     lib.snpm_panel_f1_counts.argtypes = [p, p, i64, p, i64, i64, p, p, p]
     lib.snpm_panel_parent_counts.argtypes = [p, p, i64, p, i64, i64, p, p, i64, C.c_int32, p, p, p, p]
+    lib.snpm_panel_ibd_counts.argtypes = [p, p, i64, p, i64, i64, p, i64, C.c_int32, C.c_int32, C.c_int32, p, p, p, p, p, p, p, p, p]
     lib.snpm_panel_sim_counts.argtypes = [p, p, i64, p, i64, i64, p, i64, C.c_uint64, C.c_uint64, p, p]
     lib.snpm_panel_mosaic.argtypes = [p, p, i64, p, i64, i64, p, i64, p, i64, p, C.c_int32, p, p, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]

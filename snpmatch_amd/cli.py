@@ -14,7 +14,7 @@ the in-silico F1 of EVERY pair of accessions against a sample on the device, whe
 scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
 the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
 counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses; ``mosaic`` (not in the reference) paints a sample of more than two
-sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state.  The other reference subcommands (parser, makedb) are outside the accelerated
+sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments.  The other reference subcommands (parser, makedb) are outside the accelerated
 path.
 """
 import argparse
@@ -179,6 +179,14 @@ def snpmatch_mosaic(args):
     if args['accFile']:
         check_file(args['accFile'])
     mosaic.potatoMosaic(args)
+
+
+def snpmatch_ibd(args):
+    from .core import ibd
+    check_file(args['hdf5File'])
+    if args['accFile']:
+        check_file(args['accFile'])
+    ibd.potatoIBD(args)
 
 
 def makedb_native(args):
@@ -412,6 +420,20 @@ def get_options(description, version_message):
     mos.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     mos.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.mosaic.segments.tsv, <prefix>.mosaic.json and <prefix>.mosaic.npz")
     mos.set_defaults(func=snpmatch_mosaic)
+
+    # not in the reference: where along the genome every pair of accessions is identical (shared haplotype segments)
+    ibd = sub.add_parser('ibd', help="shared segments (identity by descent): for EVERY pair of accessions of the database the genome windows in which the two are identical, and the runs of such windows along each chromosome")
+    ibd.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    ibd.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    ibd.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    ibd.add_argument("--genome", dest="genome", default="athaliana_tair10", help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
+    ibd.add_argument("-b", "--window_size", dest="binLen", default=100000, type=int, help="window length in bp (default 100000)")
+    ibd.add_argument("--min_win_sites", dest="min_win_sites", default=20, type=int, help="a window is used for a pair only with this many rows or more at which both accessions are homozygous (default 20)")
+    ibd.add_argument("--max_diff", dest="max_diff", default=0.001, type=float, help="a used window is shared when at most this fraction of those rows differ, 0 .. 1 (default 0.001)")
+    ibd.add_argument("--min_run", dest="min_run", default=5, type=int, help="a run is reported with this many shared windows or more (default 5)")
+    ibd.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    ibd.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.ibd.npz, <prefix>.ibd.pairs.tsv, <prefix>.ibd.segments.tsv and <prefix>.ibd.json")
+    ibd.set_defaults(func=snpmatch_ibd)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

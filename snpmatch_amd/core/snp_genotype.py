@@ -434,6 +434,17 @@ class Genotype(object):
         return engine.parent_counts(_resident_panel(self, "the parent search needs"), sample_class, win_off, min_win_sites, filter_acc_ix,
                                     _rows_or_range(filter_snp_ix))
 
+    def ibd_counts(self, win_off, min_win_sites=20, max_diff_ppm=1000, min_run=1, filter_acc_ix=None, filter_snp_ix=None, bits=True):
+        """the dict of ``engine.ibd_counts`` -- w_used, w_shared, n_shared, d_shared, run_max, n_runs, w_in_runs int32 [n, n] and the
+        used / shared window bitsets -- of every pair of the listed accessions over the listed DB rows grouped into windows by
+        ``win_off``, counted on the resident panel: the windows in which two accessions are identical and the runs they form.  None
+        = all accessions / all rows; ``filter_snp_ix`` may be a ``range``; a row list that is a run ``r, r + 1, ...`` is scanned as
+        a dense range."""
+        from .. import engine
+        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
+        return engine.ibd_counts(_resident_panel(self, "the shared-segment scan needs"), win_off, min_win_sites, max_diff_ppm, min_run, filter_acc_ix,
+                                 rows, bits)
+
     def sim_counts(self, grp_off, err_rate, seed, filter_acc_ix=None, filter_snp_ix=None):
         """(score, ninfo) int32 [n_grp, n, n] of the sample simulated from every listed accession (its calls at the listed DB rows,
         errors at ``err_rate`` injected under ``seed``) against every listed accession, per group of the listed rows as ``grp_off``

@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs"};
 
 struct Buf {
     void *p = nullptr;
@@ -72,6 +72,8 @@ struct Buf {
     X(ws_sim_planes) X(ws_sim_grp) X(ws_sim_cols) X(ws_sim_out)                                                                   \
     /* snpm_panel_mosaic (snpm_api_mos.hpp): bit-planes [4][cols_pad][W] of a slab of whole chains; sw words, j | state and class words of a group of samples; chain table; column list; chain_cost | col_cost */ \
     X(ws_mos_planes) X(ws_mos_sw) X(ws_mos_j) X(ws_mos_cls) X(ws_mos_chains) X(ws_mos_cols) X(ws_mos_out)                         \
+    /* snpm_panel_ibd_counts (snpm_api_ibd.hpp): bit-planes [4][cols_pad][W] of a slab; group table; step offsets; segments; column list; the seven matrices; used | shared bitsets */ \
+    X(ws_ibd_planes) X(ws_ibd_groups) X(ws_ibd_steps) X(ws_ibd_segs) X(ws_ibd_cols) X(ws_ibd_out) X(ws_ibd_bits)                  \
     /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
     /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
     X(ws_rows)                                                                                                                    \
@@ -124,6 +126,8 @@ struct snpm_ctx {
     size_t par_ws_bytes = size_t(512) << 20;    // SNPM_PAR_WS_MB: bit-planes of one slab of whole windows of snpm_panel_parent_counts
     size_t sim_ws_bytes = size_t(512) << 20;    // SNPM_SIM_WS_MB: the seven bit-planes of one row slab of snpm_panel_sim_counts
     size_t mos_ws_bytes = size_t(512) << 20;    // SNPM_MOS_WS_MB: planes of one slab of whole chains and the sw words, j and states of one group of samples of snpm_panel_mosaic
+    size_t ibd_ws_bytes = size_t(512) << 20;    // SNPM_IBD_WS_MB: bit-planes of one slab of whole windows of snpm_panel_ibd_counts
+    size_t ibd_bits_bytes = size_t(2048) << 20; // SNPM_IBD_BITS_MB: the most the two device bitsets [ncols][ncols][wwords] of snpm_panel_ibd_counts may take
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -518,6 +522,8 @@ try {
     if (const char *s = getenv("SNPM_PAR_WS_MB")) ctx->par_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_SIM_WS_MB")) ctx->sim_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_MOS_WS_MB")) ctx->mos_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_IBD_WS_MB")) ctx->ibd_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_IBD_BITS_MB")) ctx->ibd_bits_bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -675,6 +681,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_sim.hpp"
 
 #include "snpm_api_mos.hpp"
+
+#include "snpm_api_ibd.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

@@ -835,6 +835,41 @@ def parent_counts(panel, sample_class, win_off, min_win_sites=1, cols=None, rows
     return score, n_tot, w_first, w_het
 
 
+IBD_COUNT_NAMES = ("w_used", "w_shared", "n_shared", "d_shared", "run_max", "n_runs", "w_in_runs")
+
+
+def ibd_counts(panel, win_off, min_win_sites=20, max_diff_ppm=1000, min_run=1, cols=None, rows=None, bits=True):
+    """For every pair of accession columns of a resident panel the windows in which the two are identical -- shared haplotype
+    segments, identity by descent -- in one device call (``snpm_panel_ibd_counts``).  ``cols`` / ``rows`` as for
+    ``kinship_counts``; ``win_off`` [n_win + 1]: offsets into the SELECTED rows (starts at 0, never decreases, ends at the row count;
+    empty windows allowed).  Per cell (a, b) -- positions in the column list -- and window: n rows where both calls are homozygous,
+    d of them where the two differ.  A window is used with n >= ``min_win_sites`` (>= 1), shared when used and
+    d * 1 000 000 <= ``max_diff_ppm`` * n (0 .. 1 000 000), a break when used and not shared.  The windows of a call, in order, form
+    runs: shared windows without a break between them (unused windows neither break a run nor count in it); a run is reported with
+    ``min_run`` (>= 1) shared windows or more.  Returns a dict of ``w_used``, ``w_shared``, ``n_shared``, ``d_shared``, ``run_max``,
+    ``n_runs``, ``w_in_runs`` -- int32 [n_cols, n_cols], full and symmetric -- and ``used_bits`` / ``shared_bits``, uint32 [n_cols,
+    n_cols, ceil(n_win / 32)] (window w is bit w % 32 of word w // 32; None with ``bits=False``).  Group (accession-sharded) and
+    streamed panels are refused."""
+    _need_resident_panel(panel, "ibd_counts")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    win_off = np.ascontiguousarray(win_off, dtype=np.int64).reshape(-1)
+    assert len(win_off) >= 1, "win_off holds n_win + 1 entries"
+    if ncols > F1X_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_F1X_MAX_ACCESSIONS)" % (ncols, F1X_MAX_ACCESSIONS))
+    n_win = len(win_off) - 1
+    out = {name: np.empty((ncols, ncols), dtype=np.int32) for name in IBD_COUNT_NAMES}
+    out["used_bits"], out["shared_bits"] = ((np.empty((ncols, ncols, (n_win + 31) // 32), dtype=np.uint32) if bits else None) for _ in range(2))
+    check(ctx.lib.snpm_panel_ibd_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(win_off), n_win, int(min_win_sites),
+                                        int(max_diff_ppm), int(min_run), *[ptr(out[name]) for name in IBD_COUNT_NAMES + ("used_bits", "shared_bits")]), ctx.h)
+    return out
+
+
 SIM_MAX_ACCESSIONS = 11552     # SNPM_SIM_MAX_ACCESSIONS: columns of one ``sim_counts`` call
 SIM_MAX_GROUPS = 64            # groups of one ``sim_counts`` call
 
