@@ -439,7 +439,10 @@ int snpm_profile_reset(snpm_ctx *ctx);
    slab), "mos_fwd" / "mos_back" (the two kernels of snpm_panel_mosaic, one launch each per slab of whole chains and group of
    samples; its planes are a "win_planes" launch per slab), "ibd_count" / "ibd_runs" (the two kernels of snpm_panel_ibd_counts:
    "ibd_count" one launch per slab of whole windows and 65535 groups, "ibd_runs" one launch per call; its planes are a "win_planes"
-   launch per slab).  Synchronises the stream. */
+   launch per slab), "mk_planes" / "mk_gain" / "mk_pick" / "mk_update" (the four kernels of snpm_panel_marker_select: "mk_planes"
+   one launch per call, "mk_gain" and "mk_pick" one per enqueued round, "mk_update" one per enqueued round and one more for the
+   initial need; rounds are enqueued eight at a time, so up to seven of them behind the end of the loop return at once).
+   Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
 /* ---------------------------------------------------------------- genotype_cross */
@@ -791,6 +794,50 @@ int snpm_panel_ibd_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols,
                           const int64_t *win_off, int64_t n_win, int32_t min_win_sites, int32_t max_diff_ppm, int32_t min_run,
                           int32_t *w_used, int32_t *w_shared, int32_t *n_shared, int32_t *d_shared,
                           int32_t *run_max, int32_t *n_runs, int32_t *w_in_runs, uint32_t *used_bits, uint32_t *shared_bits);
+
+/* ---------------------------------------------------------------- markers */
+/* A small set of panel rows (SNPs) that SEPARATES every pair of listed accession columns -- the list to genotype (an amplicon or
+   KASP panel) so that no two accessions are confused -- chosen greedily on the RESIDENT panel (int8 or packed), all rounds inside
+   one call.  Host pointers in and out.
+     cols, row_idx / row0 / n_rows   as for snpm_panel_kinship_counts (repeats allowed; two equal columns are a pair nothing
+                       separates); a POSITION below is an index into this row selection, 0 .. n_rows - 1
+     coord, min_dist   coord [n_rows] int64 in any order, or NULL: a pick at position p makes every row r with
+                       |coord[r] - coord[p]| < min_dist ineligible (unlinked markers); min_dist >= 0, and 0 when coord is NULL
+     eligible          [n_rows] uint8, or NULL (every row): a row with eligible[r] == 0 is never picked
+     depth             1 .. 255: how many chosen rows must separate every pair
+     max_markers       picks at most (>= 0)
+   On canonical codes, row r separates the unordered pair {a, b}, a != b, when both calls are homozygous and different (code 0 in one
+   column, 1 in the other); a het, a missing call and an int8 panel's code 3 never separate.  need [ncols, ncols] (uint8, symmetric)
+   starts at depth off the diagonal and 0 on it; remaining is its sum over a < b.  A round: stop with reason 0 if remaining == 0,
+   else with reason 1 if n_chosen == max_markers; gain[r] = the pairs with need > 0 that eligible row r separates; stop with reason 2
+   if no row is eligible or the best gain is 0; pick the eligible row with the largest gain, on a tie the smallest position; record
+   it; decrement need[a][b] and need[b][a] of every pair it separates whose need is > 0; subtract the gain from remaining; the pick
+   (and its neighbourhood, see coord) becomes ineligible.  This is the textbook greedy set (multi-)cover: NOT optimal -- a smaller
+   set may exist.  What it guarantees: every pair that the eligible rows can separate depth times ends at need 0 unless max_markers
+   stopped the loop, and with reason 2 the cells with need > 0 are exactly the pairs the candidates cannot tell apart (depth times).
+   All integer: the result is one bit pattern.
+     chosen, gain_at   [max_markers] int64 / int32: positions of the picks in order and their gains; entries at and above n_chosen are
+                       not written (at most min(max_markers, n_rows) are); may be NULL when that bound is 0
+     n_chosen, remaining  one int64 each;  stop_reason  one int32: 0 all resolved, 1 max_markers reached, 2 no eligible row with gain
+     need              [ncols, ncols] uint8: the final need matrix
+     first_gain        [n_rows] int32, or NULL: the gain of round 0 of EVERY row whatever its eligibility -- the pairs the SNP
+                       separates
+   The bit-planes of all selected rows (2 bits per call) stay on the device for the whole loop -- there are no slabs: a slab walk
+   per round would read the panel again every round -- and must fit a workspace budget (1024 MiB; SNPM_MK_WS_MB, read by snpm_init):
+   a call whose n_rows * 2 * ceil(ncols / 64) * 8 bytes do not fit is refused with SNPM_ERR_BADARG, the message states both figures
+   and advises thinning the candidates.  Limits: ncols <= SNPM_MK_MAX_ACCESSIONS, n_rows < 2^31.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, depth
+   in 1 .. 255, min_dist >= 0 and 0 without coord, the limits, the output pointers -- these before the panel handle is looked at, the
+   message of a NULL panel is in snpm_last_error(NULL) -- then every column and row inside the panel (ncols == the panel's accession
+   count when cols is NULL), then the workspace budget.  Group and streamed panels have no snpm_panel handle of this kind: the
+   Python layer refuses them.  ncols < 2, n_rows == 0 or max_markers == 0 launch nothing and write the initial state: need, n_chosen
+   0, remaining, the stop reason by the rules above, first_gain zeros.  Uploads into the panel that are still in flight are waited
+   for on the device. */
+#define SNPM_MK_MAX_ACCESSIONS 4096
+int snpm_panel_marker_select(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                             const int64_t *coord, int64_t min_dist, const uint8_t *eligible, int32_t depth, int64_t max_markers,
+                             int64_t *chosen, int32_t *gain_at, int64_t *n_chosen, int64_t *remaining, int32_t *stop_reason, uint8_t *need,
+                             int32_t *first_gain);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

@@ -59,6 +59,7 @@ SYMBOLS = [
     "snpm_panel_sim_counts",
     "snpm_panel_mosaic",
     "snpm_panel_ibd_counts",
+    "snpm_panel_marker_select",
 ]
 
 _lib = None
@@ -258,6 +259,7 @@ def load():
     lib.snpm_panel_f1_counts.argtypes = [p, p, i64, p, i64, i64, p, p, p]
     lib.snpm_panel_parent_counts.argtypes = [p, p, i64, p, i64, i64, p, p, i64, C.c_int32, p, p, p, p]
     lib.snpm_panel_ibd_counts.argtypes = [p, p, i64, p, i64, i64, p, i64, C.c_int32, C.c_int32, C.c_int32, p, p, p, p, p, p, p, p, p]
+    lib.snpm_panel_marker_select.argtypes = [p, p, i64, p, i64, i64, p, i64, p, C.c_int32, i64, p, p, p, p, p, p, p]
     lib.snpm_panel_sim_counts.argtypes = [p, p, i64, p, i64, i64, p, i64, C.c_uint64, C.c_uint64, p, p]
     lib.snpm_panel_mosaic.argtypes = [p, p, i64, p, i64, i64, p, i64, p, i64, p, C.c_int32, p, p, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]

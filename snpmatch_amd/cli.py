@@ -14,7 +14,7 @@ the in-silico F1 of EVERY pair of accessions against a sample on the device, whe
 scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
 the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
 counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses; ``mosaic`` (not in the reference) paints a sample of more than two
-sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments.  The other reference subcommands (parser, makedb) are outside the accelerated
+sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments; ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused.  The other reference subcommands (parser, makedb) are outside the accelerated
 path.
 """
 import argparse
@@ -167,8 +167,9 @@ def snpmatch_simulate(args):
 def snpmatch_power(args):
     from .core import power
     check_file(args['hdf5File'])
-    if args['accFile']:
-        check_file(args['accFile'])
+    for key in ('accFile', 'sitesFile'):
+        if args.get(key):
+            check_file(args[key])
     power.potatoPower(args)
 
 
@@ -187,6 +188,15 @@ def snpmatch_ibd(args):
     if args['accFile']:
         check_file(args['accFile'])
     ibd.potatoIBD(args)
+
+
+def snpmatch_markers(args):
+    from .core import markers
+    check_file(args['hdf5File'])
+    for key in ('accFile', 'sitesFile'):
+        if args[key]:
+            check_file(args[key])
+    markers.potatoMarkers(args)
 
 
 def makedb_native(args):
@@ -398,6 +408,7 @@ def get_options(description, version_message):
     pw.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
     pw.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     pw.add_argument("--bed", dest="bed", default=None, help="draw the markers from the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
+    pw.add_argument("--sites", dest="sitesFile", default=None, help="draw the markers from the listed rows only: a file with the columns chr and pos (a <prefix>.sites.tsv of sitestats, a <prefix>.markers.tsv of markers)")
     pw.add_argument("-n", "--number_of_snps", dest="levels", required=True, help="the ladder of marker counts, increasing: 100,1000,10000 (at most 64 levels)")
     pw.add_argument("-p", "--error_rate", dest="err_rate", default=0.001, type=float, help="probability that a call of the simulated sample is redrawn from ref / alt / het (default 0.001)")
     pw.add_argument("--trials", dest="trials", default=3, type=int, help="marker ladders drawn, one device call each (default 3)")
@@ -434,6 +445,20 @@ def get_options(description, version_message):
     ibd.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     ibd.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.ibd.npz, <prefix>.ibd.pairs.tsv, <prefix>.ibd.segments.tsv and <prefix>.ibd.json")
     ibd.set_defaults(func=snpmatch_ibd)
+
+    # not in the reference: a small set of SNPs that separates every pair of accessions (the step after power)
+    mks = sub.add_parser('markers', help="a minimal marker set: SNPs chosen greedily so that every pair of accessions of the database differs at --depth of them (homozygous calls only); greedy set cover, not optimal")
+    mks.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    mks.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    mks.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    mks.add_argument("--bed", dest="bed", default=None, help="candidates: only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
+    mks.add_argument("--sites", dest="sitesFile", default=None, help="candidates: only the rows listed in a <prefix>.sites.tsv of sitestats or a <prefix>.pruned.tsv of ld (columns chr and pos)")
+    mks.add_argument("--depth", dest="depth", default=1, type=int, help="every pair must differ at this many chosen SNPs, 1 .. 255 (default 1)")
+    mks.add_argument("--max_markers", dest="max_markers", default=None, type=int, help="stop after this many SNPs (default: no limit)")
+    mks.add_argument("--min_dist_bp", dest="min_dist_bp", default=0, type=int, help="a chosen SNP excludes every candidate closer than this on its chromosome (default 0: no exclusion)")
+    mks.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    mks.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.markers.tsv, <prefix>.markers.json and <prefix>.markers.npz")
+    mks.set_defaults(func=snpmatch_markers)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -180,7 +180,12 @@ def potatoPower(args):
         if not wanted:
             raise ValueError("the accession list %s names no accession" % args['accFile'])
         acc_ix = np.array(found, dtype=np.int64)
+    if args.get('bed') and args.get('sitesFile'):
+        raise ValueError("give either --bed or --sites, not both")
     snp_ix = g.determine_snp_ix_given_bed(args['bed']) if args.get('bed') else None
+    if args.get('sitesFile'):           # a site list (chr, pos), e.g. the <prefix>.markers.tsv of the markers command
+        from .ld import read_sites, rows_of_sites
+        snp_ix = rows_of_sites(g, *read_sites(args['sitesFile']))
     study = Power(g, parse_levels(args['levels']), args.get('err_rate', 0.001), args.get('trials', 3), args.get('seed', 1),
                   args.get('lr_thres', LR_THRES), acc_ix, snp_ix)
     log.info("power of %d accessions, levels %s, %d trials", len(study.names), study.levels, study.trials)

@@ -445,6 +445,16 @@ class Genotype(object):
         return engine.ibd_counts(_resident_panel(self, "the shared-segment scan needs"), win_off, min_win_sites, max_diff_ppm, min_run, filter_acc_ix,
                                  rows, bits)
 
+    def marker_select(self, depth=1, max_markers=None, coord=None, min_dist=0, eligible=None, filter_acc_ix=None, filter_snp_ix=None, first_gain=True):
+        """the dict of ``engine.marker_select`` -- chosen, gain_at, n_chosen, remaining, stop_reason, need, first_gain -- of the greedy
+        choice of DB rows that separate every pair of the listed accessions ``depth`` times, made on the resident panel; positions
+        are indices into the listed rows.  None = all accessions / all rows; ``filter_snp_ix`` may be a ``range``; a row list that is
+        a run ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
+        return engine.marker_select(_resident_panel(self, "the marker selection needs"), depth, max_markers, coord, min_dist, eligible, filter_acc_ix,
+                                    rows, first_gain)
+
     def sim_counts(self, grp_off, err_rate, seed, filter_acc_ix=None, filter_snp_ix=None):
         """(score, ninfo) int32 [n_grp, n, n] of the sample simulated from every listed accession (its calls at the listed DB rows,
         errors at ``err_rate`` injected under ``seed``) against every listed accession, per group of the listed rows as ``grp_off``

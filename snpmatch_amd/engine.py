@@ -870,6 +870,55 @@ def ibd_counts(panel, win_off, min_win_sites=20, max_diff_ppm=1000, min_run=1, c
     return out
 
 
+MK_MAX_ACCESSIONS = 4096       # SNPM_MK_MAX_ACCESSIONS: columns of one ``marker_select`` call
+MK_NO_LIMIT = 2 ** 62           # ``max_markers=None``
+MK_STOP_REASONS = ("all pairs resolved", "max_markers reached", "no eligible row with gain")
+
+
+def marker_select(panel, depth=1, max_markers=None, coord=None, min_dist=0, eligible=None, cols=None, rows=None, first_gain=True):
+    """A small set of rows (SNPs) of a resident panel that separates every pair of the listed accession columns ``depth`` times,
+    chosen greedily on the device, all rounds in one call (``snpm_panel_marker_select``).  ``cols`` / ``rows`` as for
+    ``kinship_counts``; a *position* is an index into the row selection.  A row separates a pair when both calls are homozygous and
+    different.  Per round the eligible row that separates the most pairs still in need is picked (ties: the smallest position), the
+    need of those pairs drops by one, and the pick becomes ineligible -- with ``coord`` (int64, one per selected row, any order) every
+    row with ``|coord[r] - coord[pick]| < min_dist`` as well; ``eligible`` (one byte per selected row, 0 = never pick) masks rows from
+    the start; ``max_markers`` (None: no limit) bounds the picks.  This is the textbook greedy set cover: not optimal, a smaller
+    set may exist.  Returns a dict: ``chosen`` int64 [n_chosen] (positions, in pick order), ``gain_at`` int32 [n_chosen], ``n_chosen``,
+    ``remaining`` (the sum of need over a < b), ``stop_reason`` (0 all pairs resolved, 1 ``max_markers`` reached, 2 no eligible row
+    with gain: the cells of ``need`` > 0 are then the pairs the candidates cannot tell apart), ``need`` uint8 [n_cols, n_cols] and
+    ``first_gain`` int32 [n_rows] (the pairs every row separates, whatever its eligibility; None with ``first_gain=False``; zeros from
+    a call with fewer than two columns, no row or ``max_markers`` 0, which launches nothing).  Group (accession-sharded) and streamed
+    panels are refused."""
+    _need_resident_panel(panel, "marker_select")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    if ncols > MK_MAX_ACCESSIONS:           # the library's limit, before numpy is asked for the result arrays
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_MK_MAX_ACCESSIONS)" % (ncols, MK_MAX_ACCESSIONS))
+    max_markers = MK_NO_LIMIT if max_markers is None else int(max_markers)
+    if coord is not None:
+        coord = np.ascontiguousarray(coord, dtype=np.int64).reshape(-1)
+        assert len(coord) == n_rows, "coord holds one entry per selected row"
+    if eligible is not None:
+        eligible = np.ascontiguousarray(np.asarray(eligible).reshape(-1) != 0, dtype=np.uint8)
+        assert len(eligible) == n_rows, "eligible holds one entry per selected row"
+    cap = max(0, min(max_markers, n_rows))
+    chosen, gain_at = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int32)
+    need = np.empty((ncols, ncols), dtype=np.uint8)
+    first = np.empty(n_rows, dtype=np.int32) if first_gain else None
+    n_chosen, remaining, reason = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(ctx.lib.snpm_panel_marker_select(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(coord), int(min_dist), ptr(eligible), int(depth),
+                                           max_markers, ptr(chosen), ptr(gain_at), C.byref(n_chosen), C.byref(remaining), C.byref(reason), ptr(need),
+                                           ptr(first)), ctx.h)
+    n = int(n_chosen.value)
+    return {"chosen": chosen[:n].copy(), "gain_at": gain_at[:n].copy(), "n_chosen": n, "remaining": int(remaining.value),
+            "stop_reason": int(reason.value), "need": need, "first_gain": first}
+
+
 SIM_MAX_ACCESSIONS = 11552     # SNPM_SIM_MAX_ACCESSIONS: columns of one ``sim_counts`` call
 SIM_MAX_GROUPS = 64            # groups of one ``sim_counts`` call
 
