@@ -293,8 +293,10 @@ int snpm_host_free(snpm_ctx *ctx, void *ptr);
    snpm_carry that holds the running totals:
      STRICT  the chain of additions continues across slabs: fp64 bits of the reference over the whole job;
      EXACT / FAST  fast pass per slab, totals added in slab order; the error bounds of the slabs add up
-             (chunks_after = number of `chunk`-row pieces in the slabs still to come, they lengthen the reference's
-             chain) and snpm_carry_finish certifies the TOTALS: it returns the accessions whose int(score) is not
+             (every addition of the reference's chain is charged in the slab where it happens, by the magnitude
+             the totals of the slabs scored so far allow; chunks_after = number of `chunk`-row pieces in the slabs
+             still to come: non-zero says that this slab is not the last one and must end on a chunk boundary)
+             and snpm_carry_finish certifies the TOTALS: it returns the accessions whose int(score) is not
              yet proven.  For those the caller streams the slabs once more through a second, column-list carry
              (snpm_carry_set_columns + snpm_query_run_carry in STRICT mode) and patches the result in
              (snpm_carry_patch); more than 64 flagged: a second pass in STRICT mode over all accessions.

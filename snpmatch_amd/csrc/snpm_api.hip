@@ -230,6 +230,8 @@ struct snpm_query {
     // certificate state, all on the device: one small block {double eref; int count; int pad; int32 cols[REEVAL_CAP]}
     void *d_cert = nullptr;
     int64_t eref_chunk = -1, eref_after = -1;   // what d_cert->eref currently holds
+    double *d_csum = nullptr;           // slab-carry jobs: sum of wmax over each chunk of csum_chunk rows (k_chunk_sums), made on first use
+    int64_t csum_chunk = -1;
     bool count_valid = false;           // the last run was a certified one (count / cols are meaningful)
     bool cert_count_clean = false;      // the flag count is already zero (k_once_prep cleared it): run_fast skips its fill, once
     std::vector<snpm_ctx::Cached> owned;   // every device buffer of this query with its capacity
@@ -550,6 +552,7 @@ static void orphan_query(snpm_query *q, bool use_hip)
     }
     q->d_row_idx = nullptr; q->d_w = nullptr; q->d_lut = nullptr; q->d_score = nullptr; q->d_ninfo = nullptr;
     q->own_score = nullptr; q->own_ninfo = nullptr; q->d_wbits = nullptr; q->d_cert = nullptr;
+    q->d_csum = nullptr; q->csum_chunk = -1;
     q->panel = nullptr;
 }
 

@@ -97,6 +97,10 @@ int snpm_carry_set_columns(snpm_carry *c, const int32_t *cols, int64_t ncols)
     return SNPM_OK;
 }
 
+// the reference-order bound of the slab being added (k_echain -> k_carry_add), in the carry's device block: {double E; int ncols;
+// int pad; double E_slab; ...; int32 cols[] at 256}
+static double *carry_e_slab(const snpm_carry *c) { return (double *)((char *)c->d_E + 16); }
+
 int snpm_query_run_carry(snpm_query *q, int64_t chunk, int skip_hets, int mode, int64_t chunks_after, snpm_carry *c)
 try {
     CHECK_QUERY(q);
@@ -138,16 +142,18 @@ try {
         if (rc) return rc;
         // The job's bound takes the reference-order term of EVERY slab: a slab of integer weights is exact on its own
         // (run_fast skips its bound), but in a job that also holds non-integer slabs the reference adds this slab's chunk
-        // sums onto a non-integer running total, so its terms pick up gamma(chunks left) like any others.  Only a job
+        // sums onto a non-integer running total, so its chain additions round like any others.  Only a job
         // whose slabs are all integer is exact in any order (snpm_carry_finish then flags nothing).
+        // Every chain addition is charged here, in the slab where it happens, by the magnitude the running total can have
+        // by then (k_echain: c->wsum so far is W_before), so the chunks still to come no longer enter the term.
         const bool bounded = cert.on && q->n > 0;
-        if (bounded && q->all_integer) {
-            rc = ensure_eref(q, chunk, chunks_after);
+        if (bounded) {
+            rc = run_echain(q, chunk, (double)(c->wsum * 1.0000001L), carry_e_slab(c));
             if (rc) return rc;
         }
         hipLaunchKernelGGL(k_carry_add, dim3((unsigned)((p->n_acc + 255) / 256)), dim3(256), 0, ctx->stream, c->d_score,
                            c->d_ninfo, (const double *)q->d_score, (const int64_t *)q->d_ninfo, p->n_acc, c->d_E,
-                           bounded ? (const double *)q->cert_eref() : (const double *)nullptr,
+                           bounded ? (const double *)carry_e_slab(c) : (const double *)nullptr,
                            (bounded && !q->all_integer) ? efast_bound(q, g) : 0.0);
         HIPCHK(ctx, hipGetLastError());
         c->all_integer = c->all_integer && (q->all_integer || q->n == 0);

@@ -4,7 +4,8 @@
 // For sums of terms x_i with |x_i| <= wmax_i, a computed sum differs from the exact one by at most
 // sum_i wmax_i * gamma(m_i), gamma(m) = m*u/(1-m*u), u = 2^-53, m_i = number of fp64 additions the
 // term passes through.  Reference order: m_i <= (rows of its chunk) + 3 + (chunks left, later slabs included):
-// k_eref / k_efinish evaluate that sum where the weights live and leave it in q->cert_eref()[0].
+// k_eref / k_efinish evaluate that sum where the weights live and leave it in q->cert_eref()[0].  Slab-streamed jobs
+// (snpm_query_run_carry) charge the chain additions by the magnitude of the running total instead: run_echain.
 int ensure_pinned(snpm_ctx *ctx, size_t bytes)
 {
     if (ctx->h_pinned_cap >= bytes) return SNPM_OK;
@@ -38,6 +39,33 @@ int ensure_eref(snpm_query *q, int64_t chunk, int64_t chunks_after)
     return SNPM_OK;
 }
 
+// Slab-carry jobs: the reference-order bound of this slab behind earlier slabs whose wmax sum to w_before, left in *e_slab (a
+// buffer of the carry: q->cert_eref() belongs to run_fast's certificate of resident queries).  The chunk sums are a pass over
+// the weights and are kept per (query, chunk); the one-block k_echain runs on every call, for w_before changes from job to job.
+int run_echain(snpm_query *q, int64_t chunk, double w_before, double *e_slab)
+{
+    snpm_ctx *ctx = q->panel->ctx;
+    const int64_t K = (q->n + chunk - 1) / chunk;
+    if (q->csum_chunk != chunk) {
+        if (q->d_csum) query_release(q, q->d_csum);
+        q->d_csum = nullptr;
+        q->csum_chunk = -1;
+        if (query_alloc(q, (void **)&q->d_csum, (size_t)K * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            q->d_csum = nullptr;
+            return set_err(ctx, SNPM_ERR_OOM, "no memory for the chunk sums of the error bound");
+        }
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(K, 2048));
+        hipLaunchKernelGGL(k_chunk_sums, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)q->d_w, q->n, chunk,
+                           q->d_csum);
+        HIPCHK(ctx, hipGetLastError());
+        q->csum_chunk = chunk;
+    }
+    hipLaunchKernelGGL(k_echain, dim3(1), dim3(ECHAIN_THREADS), 0, ctx->stream, (const double *)q->d_csum, q->n, chunk, w_before, e_slab);
+    HIPCHK(ctx, hipGetLastError());
+    return SNPM_OK;
+}
+
 double efast_bound(const snpm_query *q, const FastGeom &g)
 {
     const double u = 1.1102230246251565e-16;
@@ -46,7 +74,12 @@ double efast_bound(const snpm_query *q, const FastGeom &g)
     // kernels add pre-summed quads of rows or run on integer weights only: the static_asserts beside Q4_RUN keep them below
     // EPOCH_TILES * TILE_ROWS additions per epoch)
     const int64_t epoch_adds = (int64_t)EPOCH_TILES * (g.packed ? TILE_ROWS : std::max(g.tile_rows, TILE_ROWS));
-    const double m = (double)(std::min<int64_t>(g.part_rows, epoch_adds) + REDUCE_GROUP + g.n_groups + 2);
+    int64_t part_adds = std::min<int64_t>(g.part_rows, epoch_adds);
+    // two-level launches (k_fast<..., TWO>): one addition per row of the term's tile, then one per tile of its epoch
+    if (g.two_level && !g.packed)
+        part_adds = std::min<int64_t>(part_adds, std::min<int64_t>(g.part_rows, g.tile_rows) +
+                                                     std::min<int64_t>(g.part_rows / g.tile_rows, EPOCH_TILES));
+    const double m = (double)(part_adds + REDUCE_GROUP + g.n_groups + 2);
     return (q->wsum * (m * u / (1.0 - m * u))) * 1.0000001;
 }
 
@@ -121,6 +154,7 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
             if (tr < TILE_ROWS) g = fast_geom(ctx, p->n_acc, q->n, occ, p16, (int)tr, wpb_fixed, kmult);
         }
     }
+    g.two_level = fast_two_level(ctx, p, g, skip != 0, gather);
     if (geom_out) *geom_out = g;
     q->last_kernel = bits ? "k_fast_bits" : (p16 ? "k_fast_packed_q4" : "k_fast");
     rc = ensure(ctx, ctx->ws_part_score, (size_t)g.n_slots * p->ld * sizeof(double));
@@ -132,7 +166,7 @@ int run_fast(snpm_query *q, int skip, FastGeom *geom_out, const Certify &cert)
     rc = ensure(ctx, ctx->ws_grp_miss, (size_t)g.n_groups * p->ld * sizeof(uint32_t));
     if (rc) return rc;
     const bool certify = cert.on && !q->all_integer && q->n > 0;
-    if (certify) {
+    if (certify && cert.flag) {         // (slab jobs, flag == false, take their reference-order term from run_echain)
         rc = ensure_eref(q, cert.chunk, cert.chunks_after);
         if (rc) return rc;
     }

@@ -7,6 +7,8 @@ struct FastGeom {
     int tile_rows = TILE_ROWS;
     int64_t n_wc, n_colblocks, n_parts, part_rows;
     int64_t n_epochs, n_slots, n_groups;      // partial slots = n_epochs * n_parts, reduced in groups
+    int occ = 0;            // resident blocks per CU the part count was sized for
+    bool two_level = false; // the launch is k_fast<..., TWO>: tile sums folded into epoch sums (run_fast sets it, efast_bound reads it)
 };
 
 template <bool SKIP, bool GATHER>
@@ -86,6 +88,7 @@ FastGeom fast_geom(snpm_ctx *ctx, int64_t n_acc, int64_t n, int occ_blocks_hint,
     if (ctx->debug_max_parts > 0) n_parts = std::min<int64_t>(n_parts, ctx->debug_max_parts);   // tests: long parts
     n_parts = std::min<int64_t>(n_parts, 65535);             // grid.y
     g.n_parts = n_parts;
+    g.occ = occ * narrow_mult * kmult;
     const int64_t tiles_per_part = (n_tiles + n_parts - 1) / n_parts;
     g.part_rows = tiles_per_part * tile_rows;                // rows per part (upper bound)
     g.n_epochs = std::max<int64_t>(1, (tiles_per_part + EPOCH_TILES - 1) / EPOCH_TILES);
@@ -108,6 +111,17 @@ int launch_fast_t(snpm_query *q, const FastGeom &g)
     dim3 grid((unsigned)g.n_colblocks, (unsigned)g.n_parts);
     dim3 block(WAVE * g.wpb);
     ProfScope ps(ctx, PK_FAST);
+    if constexpr (!GATHER) {
+        if (g.two_level) {                      // dense long scans whose residency allows it (fast_two_level): two-level sums
+            if (g.tile_rows != LONG_TILE_ROWS) return set_err(ctx, SNPM_ERR_STATE, "two-level sums need long tiles");
+            hipLaunchKernelGGL((k_fast<SKIP, false, false, LONG_TILE_ROWS, PAD, true>), grid, block, 0, ctx->stream, p->d,
+                               p->pitch, q->d_row_idx, q->row0, q->n, q->d_lut, (double *)ctx->ws_part_score.p,
+                               (uint32_t *)ctx->ws_part_miss.p, p->ld, p->n_acc, (const int64_t *)nullptr);
+            HIPCHK(ctx, hipGetLastError());
+            return SNPM_OK;
+        }
+    }
+    if (g.two_level) return set_err(ctx, SNPM_ERR_STATE, "two-level sums on a gathered launch");
     if (g.tile_rows == LONG_TILE_ROWS)          // long scans: tiles of LONG_TILE_ROWS rows (fast_tile_rows)
         hipLaunchKernelGGL((k_fast<SKIP, GATHER, false, LONG_TILE_ROWS, PAD>), grid, block, 0, ctx->stream, p->d,
                            p->pitch, q->d_row_idx, q->row0, q->n, q->d_lut, (double *)ctx->ws_part_score.p, (uint32_t *)ctx->ws_part_miss.p,
@@ -130,6 +144,36 @@ int launch_fast_b(snpm_query *q, const FastGeom &g, bool skip, bool gather)
     if (skip)
         return gather ? launch_fast_t<true, true, false>(q, g) : launch_fast_t<true, false, false>(q, g);
     return gather ? launch_fast_t<false, true, false>(q, g) : launch_fast_t<false, false, false>(q, g);
+}
+
+// Two-level sums (k_fast<..., TWO>) for this launch?  Dense rows on long tiles only, and only where the kernel's 77 VGPRs (6
+// waves per SIMD against 7) still let a CU hold every block the geometry sized its parts for: the flagship's two 8-wave
+// blocks and the capped 4- and 5-wave blocks of long scans do, full-occupancy blocks of 3, 4, 5 and 7 waves would lose one
+// resident block per CU (and leave a tail of parts behind the others) and stay on the single-level kernel, as does every
+// launch when the occupancy query fails.  A launch of fewer blocks than that needs what it has, not what would fit.
+static bool fast_two_level(const snpm_ctx *ctx, const snpm_panel *p, const FastGeom &g, bool skip, bool gather)
+{
+    if (g.packed || gather || g.tile_rows != LONG_TILE_ROWS) return false;
+    static int occ_cache[2][2][MAX_WAVES_PER_BLOCK + 1];      // 0: not asked yet, -1: the query failed (one gfx target: same on every device)
+    const bool pad = fast_has_pad_line(p);
+    int &c = occ_cache[skip ? 1 : 0][pad ? 1 : 0][g.wpb];
+    if (c == 0) {
+        int nb = 0;
+        hipError_t e;
+        const int thr = WAVE * g.wpb;
+        if (skip)
+            e = pad ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast<true, false, false, LONG_TILE_ROWS, true, true>, thr, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast<true, false, false, LONG_TILE_ROWS, false, true>, thr, 0);
+        else
+            e = pad ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast<false, false, false, LONG_TILE_ROWS, true, true>, thr, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fast<false, false, false, LONG_TILE_ROWS, false, true>, thr, 0);
+        if (e != hipSuccess) (void)hipGetLastError();
+        c = (e == hipSuccess && nb > 0) ? nb : -1;
+    }
+    const int64_t blocks = g.n_parts * g.n_colblocks;
+    const int64_t per_cu = std::min<int64_t>(g.occ, (blocks + ctx->n_cu - 1) / std::max(1, ctx->n_cu));
+    // (the launch bound alone promises SNPM_FAST_MIN_WAVES waves on each of the four SIMDs: both counts have to agree)
+    return c >= per_cu && per_cu * g.wpb <= 4 * SNPM_FAST_MIN_WAVES;
 }
 
 // block shape of k_fast_packed_q4 (a wave covers 1024 accessions): see run_fast

@@ -78,12 +78,20 @@ __device__ __forceinline__ void load_row(const int8_t *p, uint32_t (&x)[1])
 // [part_desc[3p], part_desc[3p+1]) of the (concatenated) matched list -- never more than EPOCH_TILES tiles, all inside
 // one segment -- and writes its partial sums to slot part_desc[3p+2]; k_reduce_seg adds the slots of a segment in
 // order.  Without SEG the arguments part_desc is unused and the code is the tile-interleaved pass described above.
-template <bool SKIP, bool GATHER, bool SEG = false, int TR = TILE_ROWS, bool PAD = false>
+// TWO (two-level sums; dense long-tile launches only): the per-row sums of a tile are folded into a sum of the epoch at the tile's
+// flush, where the byte counters of missing calls are folded too, and the epoch sum is what store_partials writes.  A term then
+// passes through <= TR additions of its tile and <= EPOCH_TILES of its epoch instead of <= EPOCH_TILES * TR: the fast pass's
+// share of the exact-mode bound falls from gamma(~15 960) to gamma(~400) on a long scan (efast_bound), and with it the number
+// of totals the certificate sends to the second pass.  Cost: EPL more fp64 registers (77 VGPRs against 69: 6 resident waves
+// per SIMD instead of 7) and EPL additions per tile.  The host takes it only where the launch keeps every resident block it
+// counts on (fast_two_level); every other instantiation compiles to the code it always was.
+template <bool SKIP, bool GATHER, bool SEG = false, int TR = TILE_ROWS, bool PAD = false, bool TWO = false>
 __global__ void __launch_bounds__(WAVE *MAX_WAVES_PER_BLOCK, SNPM_FAST_MIN_WAVES)
 k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__ row_idx, int64_t row0, int64_t n,
        const double *__restrict__ lut, double *__restrict__ out_score, uint32_t *__restrict__ out_miss, int64_t ld,
        int64_t n_acc, const int64_t *__restrict__ part_desc = nullptr, int tile_rows_rt = 0)
 {
+    static_assert(!TWO || (!GATHER && !SEG && TR == LONG_TILE_ROWS), "two-level sums: dense long-tile launches only");
     // BPL = bytes (= accessions = accumulators) per lane and row: one dword.  8 and 16 B per lane streamed at 4.4 and 5.3 TB/s
     // against 6.5 TB/s (10k x 6.25M panel, round 1) and were removed; packed panels have their own kernels below
     constexpr int BPL = 4;
@@ -119,10 +127,13 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
     const int64_t n_tiles_total = (rend - rbase + TRR - 1) / TRR;
 
     double acc[EPL];
+    double hi[TWO ? EPL : 1];               // TWO: sums of the epoch; acc holds the sums of the current tile only
     uint32_t miss16[NDW * 2];               // packed 2 x u16 per register, flushed from packed u8 every tile
     uint32_t miss8[NDW];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) acc[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < (TWO ? EPL : 1); ++i) hi[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < NDW * 2; ++i) miss16[i] = 0;
 #pragma unroll
@@ -142,13 +153,17 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
         return rowbase + off;
     };
 
-    // write this lane's partial sums to slot (epoch, part) and restart them
+    // write this lane's partial sums to slot (epoch, part) and restart them (TWO: the epoch sums; acc is zero at every call,
+    // the tile flush has just folded it)
     auto store_partials = [&](int64_t epoch) {
         if (lane_on) {
             double *os = out_score + (slot0 + epoch * slot_stride) * ld + col0;
             uint32_t *om = out_miss + (slot0 + epoch * slot_stride) * ld + col0;
 #pragma unroll
-            for (int i = 0; i < EPL; i += 2) *reinterpret_cast<double2 *>(os + i) = make_double2(acc[i], acc[i + 1]);
+            for (int i = 0; i < EPL; i += 2) {
+                if constexpr (TWO) *reinterpret_cast<double2 *>(os + i) = make_double2(hi[i], hi[i + 1]);
+                else *reinterpret_cast<double2 *>(os + i) = make_double2(acc[i], acc[i + 1]);
+            }
 #pragma unroll
             for (int k = 0; k < NDW; ++k) {
                 uint4 m;
@@ -161,6 +176,10 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
         }
 #pragma unroll
         for (int i = 0; i < EPL; ++i) acc[i] = 0.0;
+        if constexpr (TWO) {
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) hi[i] = 0.0;
+        }
 #pragma unroll
         for (int i = 0; i < NDW * 2; ++i) miss16[i] = 0;
     };
@@ -260,6 +279,13 @@ k_fast(const int8_t *__restrict__ db, int64_t pitch, const int64_t *__restrict__
                 miss16[2 * k + 0] += miss8[k] & 0x00ff00ffu;          // bytes 0 and 2
                 miss16[2 * k + 1] += (miss8[k] >> 8) & 0x00ff00ffu;   // bytes 1 and 3
                 miss8[k] = 0;
+            }
+            if constexpr (TWO) {                                     // the tile's sums join the epoch's
+#pragma unroll
+                for (int i = 0; i < EPL; ++i) {
+                    hi[i] += acc[i];
+                    acc[i] = 0.0;
+                }
             }
 #if !defined(SNPM_FAST_PATTERN_ONLY) || SNPM_FAST_PATTERN_ONLY != 2
             if (more) {

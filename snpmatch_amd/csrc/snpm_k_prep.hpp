@@ -104,6 +104,108 @@ k_efinish(const double *__restrict__ partial, int n_partial, int64_t n, int64_t 
     }
 }
 
+// Slab-carry jobs (snpm_query_run_carry, exact mode): the reference-order bound of one slab with the chain additions charged
+// by the magnitude the running total can have when they happen (DESIGN.md "Exactness"):
+//   k_chunk_sums  s_k = sum of wmax over chunk k, one value per chunk (a pass over the weights: once per query and chunk size);
+//   k_echain      one block: E_slab = u' sum_k s_k (len_k + 3)  +  u sum_k P2((W_before + s_1 + ... + s_k)(1 + 1e-7)),
+//                 P2(x) = x rounded down to a power of two, u' = u / (1 - (chunk + 3) u), the whole rounded up by 1e-7.
+//                 Addition k of the reference's chain (ScoreList += chunk sums) rounds a result of magnitude <= W_before + s_1
+//                 + ... + s_k, so it errs by at most half an ulp of that binade, u P2(.); the errors of additions add up
+//                 without amplification.  W_before is the sum of wmax over all earlier slabs of the job (host, rounded up).
+//                 Thread t walks the chunks [t L, (t + 1) L), L = ceil(K / 1024), behind a block-wide prefix sum of its share.
+__global__ void __launch_bounds__(256)
+k_chunk_sums(const double *__restrict__ w, int64_t n, int64_t chunk, double *__restrict__ csum)
+{
+    __shared__ double sm[4];
+    const int64_t K = (n + chunk - 1) / chunk;
+    for (int64_t k = blockIdx.x; k < K; k += gridDim.x) {
+        const int64_t r0 = k * chunk, r1 = (r0 + chunk < n) ? r0 + chunk : n;
+        double s = 0.0;
+        for (int64_t r = r0 + threadIdx.x; r < r1; r += 256)
+            s += fmax(fabs(w[3 * r]), fmax(fabs(w[3 * r + 1]), fabs(w[3 * r + 2])));
+        s = block_sum_256(s, sm);
+        if (threadIdx.x == 0) csum[k] = s;
+    }
+}
+
+__device__ __forceinline__ double pow2_floor(double x)      // x >= 0 finite: the power of two at or below x (0 below the normal range)
+{
+    return __longlong_as_double(__double_as_longlong(x) & 0x7ff0000000000000ll);
+}
+
+constexpr int ECHAIN_THREADS = 1024;
+constexpr int ECHAIN_BATCH = 8;          // chunk sums a thread requests at once: the loops are bound by the latency of their loads
+
+__global__ void __launch_bounds__(ECHAIN_THREADS)
+k_echain(const double *__restrict__ csum, int64_t n, int64_t chunk, double w_before, double *__restrict__ e_slab)
+{
+    constexpr int NW = ECHAIN_THREADS / 64, NB = ECHAIN_BATCH;
+    __shared__ double s_wave[NW], s_in[NW], s_ch[NW];
+    const int64_t K = (n + chunk - 1) / chunk;
+    const int64_t L = (K + ECHAIN_THREADS - 1) / ECHAIN_THREADS;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t k0 = (int64_t)t * L < K ? (int64_t)t * L : K;
+    const int64_t k1 = k0 + L < K ? k0 + L : K;
+    double mine = 0.0;
+    for (int64_t k = k0; k < k1; k += NB) {
+        double v[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) v[j] = (k + j < k1) ? csum[k + j] : 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) mine += v[j];
+    }
+    // exclusive prefix of `mine` over the threads: inside the wave by shuffles, the wave totals through LDS
+    double incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    // (the sum of the lanes before this one, not incl - mine: a difference would lose a small prefix in front of a large share)
+    double excl = __shfl_up(incl, 1);
+    if (lane == 0) excl = 0.0;
+    __syncthreads();
+    double before = w_before;
+    for (int wv = 0; wv < wave; ++wv) before += s_wave[wv];
+    double run = before + excl;
+    double in_chunk = 0.0, chain = 0.0;
+    for (int64_t k = k0; k < k1; k += NB) {
+        double v[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) v[j] = (k + j < k1) ? csum[k + j] : 0.0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            if (k + j < k1) {
+                const int64_t len = (k + j == K - 1) ? n - (K - 1) * chunk : chunk;
+                in_chunk += v[j] * (double)(len + 3);
+                run += v[j];
+                chain += pow2_floor(run * 1.0000001);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        in_chunk += __shfl_xor(in_chunk, o);
+        chain += __shfl_xor(chain, o);
+    }
+    if (lane == 0) {
+        s_in[wave] = in_chunk;
+        s_ch[wave] = chain;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double a = 0.0, c = 0.0;
+        for (int wv = 0; wv < NW; ++wv) {
+            a += s_in[wv];
+            c += s_ch[wv];
+        }
+        const double u = 1.1102230246251565e-16;
+        const double mmax = (double)(chunk + 3);
+        e_slab[0] = (a * u / (1.0 - mmax * u) + c * u) * 1.0000001;
+    }
+}
+
 // row lists that arrive without a host pass over them (batches): entries outside the panel are replaced by row 0 --
 // no kernel ever reads outside the panel -- and reported through *bad (the call then fails after its synchronisation).
 // src32 != NULL: the list crossed PCIe as int32 (half the bytes; -1 stands for any value that does not fit) and is

@@ -26,7 +26,8 @@
 //              launch; k_reduce_seg / k_eseg_part + k_eseg_finish / k_strict_pairs / k_scan_pairs: per-segment reduce, error bound, and the
 //              reference-order re-evaluation of the (segment, accession) pairs the certificate flags.
 //   certificate  k_wprops (weight properties), k_eref / k_efinish (reference-order error bound on the device),
-//              flag_if_uncertain inside k_reduce / k_carry_flag; the re-evaluation kernels read the flag count on the
+//              k_chunk_sums / k_echain (the same bound for one slab of a slab-streamed job, chain additions charged by the
+//              magnitude of the running total), flag_if_uncertain inside k_reduce / k_carry_flag; the re-evaluation kernels read the flag count on the
 //              device and leave at once when their tier has nothing to do (dense_tier_off, *d_ncols).
 //   k_carry_add / k_carry_flag / k_tot_seg  running totals of slab-streamed jobs, totals over windows.
 //   k_likelihood  likeliTest + nanmin + ratio on device (core/snpmatch.py:40-55,106-117).
@@ -53,7 +54,7 @@
 // constants and helpers of earlier ones):
 #pragma once
 #include "snpm_k_common.hpp"      // build switches, constants
-#include "snpm_k_prep.hpp"        // k_build_lut, k_wprops, k_wbits, k_eref / k_efinish, k_check_rows, k_expand_codes
+#include "snpm_k_prep.hpp"        // k_build_lut, k_wprops, k_wbits, k_eref / k_efinish, k_chunk_sums / k_echain, k_check_rows, k_expand_codes
 #include "snpm_k_fast.hpp"        // k_fast
 #include "snpm_k_packed.hpp"      // k_fast_packed_q4, k_fast_bits
 #include "snpm_k_reduce.hpp"      // k_reduce*, k_carry_*, k_eseg_*, k_reduce_seg, k_strict_pairs, k_scan_pairs, k_tot_seg, helpers
