@@ -443,7 +443,9 @@ int snpm_profile_reset(snpm_ctx *ctx);
    "ibd_count" one launch per slab of whole windows and 65535 groups, "ibd_runs" one launch per call; its planes are a "win_planes"
    launch per slab), "mk_planes" / "mk_gain" / "mk_pick" / "mk_update" (the four kernels of snpm_panel_marker_select: "mk_planes"
    one launch per call, "mk_gain" and "mk_pick" one per enqueued round, "mk_update" one per enqueued round and one more for the
-   initial need; rounds are enqueued eight at a time, so up to seven of them behind the end of the loop return at once).
+   initial need; rounds are enqueued eight at a time, so up to seven of them behind the end of the loop return at once),
+   "pca_gram" / "pca_fold" (the two kernels of snpm_panel_gram, one launch each per slab; its planes are a "win_planes" launch per
+   slab), "pca_load" (the kernel of snpm_panel_loadings, one launch per slab).
    Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
@@ -840,6 +842,44 @@ int snpm_panel_marker_select(snpm_panel *panel, const int32_t *cols, int64_t nco
                              const int64_t *coord, int64_t min_dist, const uint8_t *eligible, int32_t depth, int64_t max_markers,
                              int64_t *chosen, int32_t *gain_at, int64_t *n_chosen, int64_t *remaining, int32_t *stop_reason, uint8_t *need,
                              int32_t *first_gain);
+
+/* ---------------------------------------------------------------- pca */
+/* The two device primitives of a principal component analysis of the RESIDENT panel (int8 or packed): the weighted Gram matrix of
+   the accession columns over panel rows -- the genotype relationship matrix before its division by the row count -- and the
+   row-streaming product that turns eigenvectors into SNP loadings.  The package's own: the reference has no counterpart (its
+   calc_kinship_mat is the count form, snpm_panel_kinship_counts).  Host pointers in and out.
+     cols, row_idx / row0 / n_rows   as for snpm_panel_kinship_counts (cols == NULL: all accessions; repeats count as listed)
+     tab [n_rows][4]   the CLASS TABLE, fp64: for selected row s the value of an accession whose canonical code is 0 (ref), 1 (alt),
+                       2 (het), 3 (an int8 panel's "other" code; a packed panel has no such code).  A missing call has value 0,
+                       always.  Write t(s, i) = tab[s][code(s, i)], or 0 where missing.
+   snpm_panel_gram:      gram[i][j] = sum over selected rows s of t(s, i) * t(s, j)      [ncols, ncols], the full symmetric matrix,
+                         diagonal included, NOT divided by n_rows
+   snpm_panel_loadings:  load[s][c] = sum over listed columns i of t(s, i) * vec[i][c]   vec [ncols, k], load [n_rows, k]
+   The arithmetic is fp64 fused multiply-add throughout.  There are no floating-point atomics: every output cell has one owner and
+   a summation order fixed by the arguments and the workspace budget, so two calls with the same arguments and settings return the
+   same bits, and gram is symmetric bit for bit.  When every partial sum is exactly representable (tables of small integers) the
+   result is the exact integer whatever the order; otherwise it differs from the exactly rounded sum by at most the bound of any
+   summation order, n * 2^-53 * sum |t| |t| (n = n_rows) resp. sum |t| |vec| (n = ncols) to first order.
+   snpm_panel_gram walks the row axis in slabs whose bit-planes (4 bits per call) and table rows fit a workspace budget (512 MiB;
+   SNPM_PCA_WS_MB, read by snpm_init; a slab is at least one step of 1024 rows whatever the budget); the matrix accumulates on the
+   device across slabs, in slab order.  Per slab a block owns a 64 x 64 tile pair for a run of plane steps (ceil(512 / tile pairs)
+   runs, 1 .. 32), rows in order within the run, and the runs of a cell are added in order.  snpm_panel_loadings reads every selected
+   row once from the panel itself, a wave per row: lane l sums columns l, l + 64, ... in order, six butterfly steps sum the lanes;
+   its slabs (table rows and results inside the same budget, at least 64 rows) do not change the order.
+   Limits: ncols <= SNPM_PCA_MAX_ACCESSIONS (kinship's: the matrix stays below 2^27 cells), 1 <= k <= SNPM_PCA_MAX_COMPONENTS,
+   n_rows < 2^31.
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, the
+   limits, gram / vec non-NULL when ncols > 0, tab / load non-NULL when ncols > 0 and n_rows > 0, every entry of tab and vec finite
+   (a NaN must never be multiplied by the 0 of a missing call) -- these before the panel handle is looked at, the message of a NULL
+   panel is in snpm_last_error(NULL) -- then every column and row inside the panel, then ncols == the panel's accession count when
+   cols is NULL.  ncols == 0 writes nothing and launches nothing; n_rows == 0 writes zeros to gram and nothing to load, without a
+   launch.  Uploads into the panel that are still in flight are waited for on the device. */
+#define SNPM_PCA_MAX_ACCESSIONS 11552
+#define SNPM_PCA_MAX_COMPONENTS 32
+int snpm_panel_gram(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                    const double *tab, double *gram);
+int snpm_panel_loadings(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                        const double *tab, const double *vec, int k, double *load);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

@@ -60,6 +60,7 @@ SYMBOLS = [
     "snpm_panel_mosaic",
     "snpm_panel_ibd_counts",
     "snpm_panel_marker_select",
+    "snpm_panel_gram", "snpm_panel_loadings",
 ]
 
 _lib = None
@@ -262,6 +263,8 @@ def load():
     lib.snpm_panel_marker_select.argtypes = [p, p, i64, p, i64, i64, p, i64, p, C.c_int32, i64, p, p, p, p, p, p, p]
     lib.snpm_panel_sim_counts.argtypes = [p, p, i64, p, i64, i64, p, i64, C.c_uint64, C.c_uint64, p, p]
     lib.snpm_panel_mosaic.argtypes = [p, p, i64, p, i64, i64, p, i64, p, i64, p, C.c_int32, p, p, p]
+    lib.snpm_panel_gram.argtypes = [p, p, i64, p, i64, i64, p, p]
+    lib.snpm_panel_loadings.argtypes = [p, p, i64, p, i64, i64, p, p, C.c_int, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]
     lib.snpm_profile_enable.argtypes = [p, ci]
     lib.snpm_profile_reset.argtypes = [p]

@@ -14,7 +14,7 @@ the in-silico F1 of EVERY pair of accessions against a sample on the device, whe
 scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
 the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
 counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses; ``mosaic`` (not in the reference) paints a sample of more than two
-sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments; ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused.  The other reference subcommands (parser, makedb) are outside the accelerated
+sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments; ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused; ``pca`` (not in the reference) makes the genotype relationship matrix of the accessions on the device (an fp64 rank-R update, every row weighted by its allele frequency), decomposes it and projects samples onto its principal axes: which part of the collection a sample that matches no accession belongs to.  The other reference subcommands (parser, makedb) are outside the accelerated
 path.
 """
 import argparse
@@ -197,6 +197,15 @@ def snpmatch_markers(args):
         if args[key]:
             check_file(args[key])
     markers.potatoMarkers(args)
+
+
+def snpmatch_pca(args):
+    from .core import pca
+    check_file(args['hdf5File'])
+    for key in ('accFile', 'popFile', 'sitesFile', 'inFile'):
+        if args[key]:
+            check_file(args[key])
+    pca.potatoPCA(args)
 
 
 def makedb_native(args):
@@ -459,6 +468,22 @@ def get_options(description, version_message):
     mks.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     mks.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.markers.tsv, <prefix>.markers.json and <prefix>.markers.npz")
     mks.set_defaults(func=snpmatch_markers)
+
+    pc = sub.add_parser('pca', help="population structure of the database: the genotype relationship matrix of its accessions and its principal components; with -i, samples projected onto them")
+    pc.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    pc.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    pc.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    pc.add_argument("--pops", dest="popFile", default=None, help="text file, accession and population per line: the union of the populations is analysed, every output row carries its population")
+    pc.add_argument("--bed", dest="bed", default=None, help="use the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
+    pc.add_argument("--sites", dest="sitesFile", default=None, help="use the listed rows only: a file with the columns chr and pos (a <prefix>.pruned.tsv of ld, a <prefix>.sites.tsv of sitestats)")
+    pc.add_argument("--min_maf", dest="min_maf", default=0.05, type=float, help="drop rows whose minor allele frequency among the analysed accessions is below this (default 0.05)")
+    pc.add_argument("--max_missing", dest="max_missing", default=0.1, type=float, help="drop rows with a larger fraction of missing calls (default 0.1)")
+    pc.add_argument("--components", dest="components", default=10, type=int, help="principal components to report, 1 .. min(32, accessions) (default 10)")
+    pc.add_argument("--keep_grm", action="store_true", dest="keep_grm", default=False, help="store the relationship matrix in <prefix>.pca.npz")
+    pc.add_argument("-i", "--input_file", dest="inFile", default=None, help="samples to project: a VCF (every sample column) or a BED file")
+    pc.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    pc.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pca.tsv, <prefix>.pca.npz, <prefix>.pca.json and, with -i, <prefix>.projection.tsv")
+    pc.set_defaults(func=snpmatch_pca)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

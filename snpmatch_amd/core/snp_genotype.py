@@ -455,6 +455,22 @@ class Genotype(object):
         return engine.marker_select(_resident_panel(self, "the marker selection needs"), depth, max_markers, coord, min_dist, eligible, filter_acc_ix,
                                     rows, first_gain)
 
+    def gram(self, tab, filter_acc_ix=None, filter_snp_ix=None):
+        """fp64 [n, n]: the Gram matrix ``sum_s t(s, i) t(s, j)`` of the listed accessions over the listed DB rows, made on the
+        resident panel (``engine.gram``).  ``tab``: fp64 [rows, 4], the value of a call with code 0 / 1 / 2 / 3 per listed row; a
+        missing call has value 0.  None = all accessions / all rows; ``filter_snp_ix`` may be a ``range``; a row list that is a run
+        ``r, r + 1, ...`` is scanned as a dense range."""
+        from .. import engine
+        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
+        return engine.gram(_resident_panel(self, "the principal component analysis needs"), tab, filter_acc_ix, rows)
+
+    def loadings(self, tab, vec, filter_acc_ix=None, filter_snp_ix=None):
+        """fp64 [rows, k]: ``sum_i t(s, i) vec[i, c]`` over the listed accessions for every listed DB row, made on the resident
+        panel (``engine.loadings``).  ``tab`` / ``filter_acc_ix`` / ``filter_snp_ix`` as for ``gram``; ``vec``: fp64 [n, k]."""
+        from .. import engine
+        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
+        return engine.loadings(_resident_panel(self, "the principal component analysis needs"), tab, vec, filter_acc_ix, rows)
+
     def sim_counts(self, grp_off, err_rate, seed, filter_acc_ix=None, filter_snp_ix=None):
         """(score, ninfo) int32 [n_grp, n, n] of the sample simulated from every listed accession (its calls at the listed DB rows,
         errors at ``err_rate`` injected under ``seed``) against every listed accession, per group of the listed rows as ``grp_off``

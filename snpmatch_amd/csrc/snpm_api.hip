@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_MK_P, PK_MK_G, PK_MK_K, PK_MK_U, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs", "mk_planes", "mk_gain", "mk_pick", "mk_update"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_MK_P, PK_MK_G, PK_MK_K, PK_MK_U, PK_PCA_G, PK_PCA_F, PK_PCA_L, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs", "mk_planes", "mk_gain", "mk_pick", "mk_update", "pca_gram", "pca_fold", "pca_load"};
 
 struct Buf {
     void *p = nullptr;
@@ -76,6 +76,8 @@ struct Buf {
     X(ws_ibd_planes) X(ws_ibd_groups) X(ws_ibd_steps) X(ws_ibd_segs) X(ws_ibd_cols) X(ws_ibd_out) X(ws_ibd_bits)                  \
     /* snpm_panel_marker_select (snpm_api_mk.hpp): row planes [n_rows][2][Wc]; Ut [Wc][cols_pad]; need; gains; block keys; eligibility; coordinates; chosen | gain_at; MkState; column list */ \
     X(ws_mk_planes) X(ws_mk_ut) X(ws_mk_need) X(ws_mk_gain) X(ws_mk_best) X(ws_mk_elig) X(ws_mk_coord) X(ws_mk_chosen) X(ws_mk_state) X(ws_mk_cols) \
+    /* snpm_panel_gram / snpm_panel_loadings (snpm_api_pca.hpp): bit-planes [4][cols_pad][W] and table rows of a slab; partials [splits][tile pairs][64][64]; the matrix; column list; vec; loadings of a slab */ \
+    X(ws_pca_planes) X(ws_pca_tab) X(ws_pca_part) X(ws_pca_out) X(ws_pca_cols) X(ws_pca_vec) X(ws_pca_load)                       \
     /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
     /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
     X(ws_rows)                                                                                                                    \
@@ -131,6 +133,7 @@ struct snpm_ctx {
     size_t ibd_ws_bytes = size_t(512) << 20;    // SNPM_IBD_WS_MB: bit-planes of one slab of whole windows of snpm_panel_ibd_counts
     size_t ibd_bits_bytes = size_t(2048) << 20; // SNPM_IBD_BITS_MB: the most the two device bitsets [ncols][ncols][wwords] of snpm_panel_ibd_counts may take
     size_t mk_ws_bytes = size_t(1024) << 20;    // SNPM_MK_WS_MB: the most the row planes of ALL selected rows of snpm_panel_marker_select may take (they stay resident for the whole loop: no slabs)
+    size_t pca_ws_bytes = size_t(512) << 20;    // SNPM_PCA_WS_MB: bit-planes and table rows of one row slab of snpm_panel_gram; table rows and results of one row slab of snpm_panel_loadings
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -530,6 +533,7 @@ try {
     if (const char *s = getenv("SNPM_IBD_WS_MB")) ctx->ibd_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_IBD_BITS_MB")) ctx->ibd_bits_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_MK_WS_MB")) ctx->mk_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_PCA_WS_MB")) ctx->pca_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -692,6 +696,8 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_ibd.hpp"
 
 #include "snpm_api_mk.hpp"
+
+#include "snpm_api_pca.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

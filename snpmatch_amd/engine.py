@@ -870,6 +870,61 @@ def ibd_counts(panel, win_off, min_win_sites=20, max_diff_ppm=1000, min_run=1, c
     return out
 
 
+PCA_MAX_ACCESSIONS = 11552     # SNPM_PCA_MAX_ACCESSIONS: columns of one ``gram`` / ``loadings`` call
+PCA_MAX_COMPONENTS = 32        # SNPM_PCA_MAX_COMPONENTS: columns of ``vec`` of one ``loadings`` call
+
+
+def _class_table(tab, n_rows):
+    tab = np.ascontiguousarray(tab, dtype=np.float64)
+    assert tab.shape == (n_rows, 4), "one row of four class values per selected row: tab is %r, %d rows selected" % (tab.shape, n_rows)
+    return tab
+
+
+def gram(panel, tab, cols=None, rows=None):
+    """The weighted Gram matrix of the accession columns of a resident panel over panel rows in one device call
+    (``snpm_panel_gram``).  ``tab``: fp64 [n_rows, 4], for every selected row the value of a call with canonical code 0 (ref), 1
+    (alt), 2 (het), 3 (an int8 panel's "other"); a missing call has value 0.  ``cols`` / ``rows`` as for ``kinship_counts``.
+    Returns fp64 [n_cols, n_cols], ``sum_s t(s, i) t(s, j)``: full, symmetric bit for bit, not divided by the row count.  fp64 FMA
+    in an order fixed by the arguments and ``SNPM_PCA_WS_MB``: the same call returns the same bits, and a table of small integers
+    gives the exact integers.  A value of ``tab`` that is not finite is refused.  Group (accession-sharded) and streamed panels
+    are refused."""
+    _need_resident_panel(panel, "gram")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    tab = _class_table(tab, n_rows)
+    if ncols > PCA_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result array
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_PCA_MAX_ACCESSIONS)" % (ncols, PCA_MAX_ACCESSIONS))
+    out = np.empty((ncols, ncols), dtype=np.float64)
+    check(ctx.lib.snpm_panel_gram(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(tab), ptr(out)), ctx.h)
+    return out
+
+
+def loadings(panel, tab, vec, cols=None, rows=None):
+    """``load[s, c] = sum_i t(s, i) vec[i, c]`` over the listed accession columns for every selected row of a resident panel, in one
+    device call (``snpm_panel_loadings``): with the eigenvectors of the Gram matrix as ``vec`` the raw SNP loadings ``Z V``.
+    ``tab`` / ``cols`` / ``rows`` as for ``gram``; ``vec``: fp64 [n_cols, k], 1 <= k <= 32, finite.  Returns fp64 [n_rows, k]."""
+    _need_resident_panel(panel, "loadings")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    tab = _class_table(tab, n_rows)
+    vec = np.ascontiguousarray(vec, dtype=np.float64)
+    assert vec.ndim == 2 and vec.shape[0] == ncols, "vec is [n_cols, k]: got %r for %d columns" % (vec.shape, ncols)
+    k = vec.shape[1]
+    out = np.zeros((n_rows, k), dtype=np.float64)
+    check(ctx.lib.snpm_panel_loadings(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(tab), ptr(vec), k, ptr(out)), ctx.h)
+    return out
+
+
 MK_MAX_ACCESSIONS = 4096       # SNPM_MK_MAX_ACCESSIONS: columns of one ``marker_select`` call
 MK_NO_LIMIT = 2 ** 62           # ``max_markers=None``
 MK_STOP_REASONS = ("all pairs resolved", "max_markers reached", "no eligible row with gain")
