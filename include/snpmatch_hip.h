@@ -445,7 +445,9 @@ int snpm_profile_reset(snpm_ctx *ctx);
    one launch per call, "mk_gain" and "mk_pick" one per enqueued round, "mk_update" one per enqueued round and one more for the
    initial need; rounds are enqueued eight at a time, so up to seven of them behind the end of the loop return at once),
    "pca_gram" / "pca_fold" (the two kernels of snpm_panel_gram, one launch each per slab; its planes are a "win_planes" launch per
-   slab), "pca_load" (the kernel of snpm_panel_loadings, one launch per slab).
+   slab), "pca_load" (the kernel of snpm_panel_loadings, one launch per slab), "adm_rows" / "adm_cols" / "adm_fold" (the three
+   kernels of snpm_panel_admix: "adm_rows" and "adm_fold" one launch per iteration, "adm_cols" one per iteration with
+   SNPM_ADMIX_UPDATE_Q).
    Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
@@ -880,6 +882,50 @@ int snpm_panel_gram(snpm_panel *panel, const int32_t *cols, int64_t ncols, const
                     const double *tab, double *gram);
 int snpm_panel_loadings(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                         const double *tab, const double *vec, int k, double *load);
+
+/* ---------------------------------------------------------------- admixture */
+/* Joint EM iterations of the admixture model (STRUCTURE, FRAPPE, ADMIXTURE) on the accession columns of the RESIDENT panel (int8 or
+   packed): every listed column is a mixture of K ancestral populations, every population has its own alt frequency at every
+   selected row.  The package's own: the reference has no counterpart.  Host pointers in and out.
+     cols, row_idx / row0 / n_rows   as for snpm_panel_gram (cols == NULL: all accessions; repeats count as listed)
+     Q [ncols][K]    the ancestry of every listed column: entries >= 0, every row summing to 1
+     F [n_rows][K]   the alt frequency of every component at every selected row, inside [SNPM_ADMIX_EPS, 1 - SNPM_ADMIX_EPS]
+   The dosage g of a call from its canonical code: ref (0) g = 0, alt (1) g = 2, het (2) g = 1.  A missing call and an int8 panel's
+   "other" code (3) are NO CALL: the cell contributes nothing anywhere.  One iteration maps (Q, F) to (Q', F'), BOTH read from the old
+   pair (joint EM: the log-likelihood never decreases).  For a called cell (s, i):
+     p = sum_k q_ik f_sk        pbar = sum_k q_ik (1 - f_sk)       both over k ascending with fma; pbar is its own positive sum,
+                                                                   never 1 - p, so v and ln pbar stay accurate where p is close to 1
+     u = g / p                  v = (2 - g) / pbar
+     ll   = sum over cells of [g > 0] g ln p + [g < 2] (2 - g) ln pbar           (the likelihood of the OLD pair)
+     a_sk = sum_i u q_ik        b_sk = sum_i v q_ik
+     c_ik = sum_s (u f_sk + v (1 - f_sk))
+     f'_sk = clamp(f a / (f a + (1 - f) b), EPS, 1 - EPS)       unchanged where the denominator is 0 (a row without a call)
+     w_ik  = q_ik c_ik;  q'_ik = w_ik / sum_k w_ik (k ascending)  unchanged where that sum is 0 (a column without a call)
+   With F inside [EPS, 1 - EPS] and the rows of Q summing to 1, p and pbar are at least EPS: no division by zero can occur.
+     flags      SNPM_ADMIX_UPDATE_F | SNPM_ADMIX_UPDATE_Q: a component that is not updated keeps its bits (it is not written);
+                flags == 0 only evaluates: loglik is written, Q and F come back untouched
+     loglik [n_iter]   loglik[t] is the likelihood of the parameters at the START of iteration t
+   Q and F are copied in once, stay on the device (double-buffered) for n_iter iterations and are copied out once.  All arithmetic
+   is fp64 with IEEE division; there are no floating-point atomics: every output has one owner and one order of summation, a
+   function of (n_rows, ncols, K) alone, so the same call returns the same bits, and n_iter = 3 returns the bits of three chained
+   calls of one iteration.  a, b: lane l of a wave sums columns l, l + 64, ... in order, butterfly steps sum the lanes.  c: the rows
+   go in contiguous runs (ceil(512 / ceil(ncols / 256)) of them, none below 16 rows), rows in order within a run, the runs are added
+   in order.  ll: the same lanes, six butterfly steps, 32 rows in order per block, then a fixed tree of radix 4 over the blocks.
+   Limits: 1 <= K <= SNPM_ADMIX_MAX_K, 1 <= n_iter <= 10000, ncols <= SNPM_PCA_MAX_ACCESSIONS, n_rows < 2^31.  There is no workspace
+   knob and there are no row slabs: F and F' take 2 x n_rows x Kp x 8 bytes on the device (Kp = 4 / 8 / 16), the row list 8 bytes
+   per row; what does not fit is reported (SNPM_ERR_OOM).
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, the
+   limits, no unknown flag bit, Q / loglik non-NULL when ncols > 0, F non-NULL when ncols > 0 and n_rows > 0, every entry of Q finite
+   and >= 0, every row sum of Q within 1e-9 of 1, every entry of F finite and inside [EPS, 1 - EPS] -- these before the panel handle is
+   looked at, the message of a NULL panel is in snpm_last_error(NULL) -- then every column and row inside the panel, then ncols ==
+   the panel's accession count when cols is NULL.  ncols == 0 writes nothing and launches nothing; n_rows == 0 writes zeros to
+   loglik, leaves Q and F, and launches nothing.  Uploads into the panel that are still in flight are waited for on the device. */
+#define SNPM_ADMIX_MAX_K 16
+#define SNPM_ADMIX_EPS 1e-6
+#define SNPM_ADMIX_UPDATE_F 1u
+#define SNPM_ADMIX_UPDATE_Q 2u
+int snpm_panel_admix(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                     int K, int n_iter, unsigned flags, double *Q, double *F, double *loglik /* [n_iter] */);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

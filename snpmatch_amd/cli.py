@@ -14,7 +14,7 @@ the in-silico F1 of EVERY pair of accessions against a sample on the device, whe
 scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
 the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
 counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses; ``mosaic`` (not in the reference) paints a sample of more than two
-sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments; ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused; ``pca`` (not in the reference) makes the genotype relationship matrix of the accessions on the device (an fp64 rank-R update, every row weighted by its allele frequency), decomposes it and projects samples onto its principal axes: which part of the collection a sample that matches no accession belongs to.  The other reference subcommands (parser, makedb) are outside the accelerated
+sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments; ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused; ``pca`` (not in the reference) makes the genotype relationship matrix of the accessions on the device (an fp64 rank-R update, every row weighted by its allele frequency), decomposes it and projects samples onto its principal axes: which part of the collection a sample that matches no accession belongs to; ``admixture`` (not in the reference) fits the admixture model of STRUCTURE / ADMIXTURE -- every accession a mixture of K ancestral populations -- by joint EM on the device, the parameters resident between iterations, and writes the population file the other panel commands take as ``--pops``.  The other reference subcommands (parser, makedb) are outside the accelerated
 path.
 """
 import argparse
@@ -197,6 +197,15 @@ def snpmatch_markers(args):
         if args[key]:
             check_file(args[key])
     markers.potatoMarkers(args)
+
+
+def snpmatch_admixture(args):
+    from .core import admixture
+    check_file(args['hdf5File'])
+    for key in ('accFile', 'popFile', 'sitesFile', 'inFile'):
+        if args[key]:
+            check_file(args[key])
+    admixture.potatoAdmixture(args)
 
 
 def snpmatch_pca(args):
@@ -484,6 +493,25 @@ def get_options(description, version_message):
     pc.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
     pc.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pca.tsv, <prefix>.pca.npz, <prefix>.pca.json and, with -i, <prefix>.projection.tsv")
     pc.set_defaults(func=snpmatch_pca)
+
+    ad = sub.add_parser('admixture', help="ancestry proportions of every accession of the database under the admixture model (K ancestral populations), fitted by EM on the device; writes a --pops file for sitestats / ld / pca; with -i, the proportions of samples")
+    ad.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
+    ad.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    ad.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
+    ad.add_argument("--pops", dest="popFile", default=None, help="text file, accession and population per line: the union of the populations is analysed, the outputs compare the clusters with them")
+    ad.add_argument("--bed", dest="bed", default=None, help="use the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
+    ad.add_argument("--sites", dest="sitesFile", default=None, help="use the listed rows only: a file with the columns chr and pos (a <prefix>.pruned.tsv of ld, a <prefix>.sites.tsv of sitestats)")
+    ad.add_argument("-K", dest="K", required=True, type=int, help="ancestral populations, 1 .. min(16, accessions)")
+    ad.add_argument("--min_maf", dest="min_maf", default=0.05, type=float, help="drop rows whose minor allele frequency among the analysed accessions is below this (default 0.05)")
+    ad.add_argument("--max_missing", dest="max_missing", default=0.1, type=float, help="drop rows with a larger fraction of missing calls (default 0.1)")
+    ad.add_argument("--seed", dest="seed", default=1, type=int, help="restart r starts from numpy.random.default_rng(seed + r) (default 1)")
+    ad.add_argument("--restarts", dest="restarts", default=1, type=int, help="runs from different starts; the one with the highest likelihood is reported (default 1)")
+    ad.add_argument("--max_iter", dest="max_iter", default=2000, type=int, help="EM iterations per restart, at most (default 2000)")
+    ad.add_argument("--tol", dest="tol", default=1e-7, type=float, help="stop when an iteration gains less than this fraction of the log-likelihood (default 1e-7)")
+    ad.add_argument("-i", "--input_file", dest="inFile", default=None, help="samples to place: a VCF (every sample column) or a BED file")
+    ad.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    ad.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.admixture.Q.tsv, .admixture.pops.tsv, .admixture.npz, .admixture.json and, with -i, <prefix>.ancestry.tsv")
+    ad.set_defaults(func=snpmatch_admixture)
 
     mk = sub.add_parser('makedb-native', help="Convert a DB (.npz / HDF5) to the native flat panel format")
     mk.add_argument("-i", "--input", dest="inFile")

@@ -471,6 +471,14 @@ class Genotype(object):
         rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
         return engine.loadings(_resident_panel(self, "the principal component analysis needs"), tab, vec, filter_acc_ix, rows)
 
+    def admix(self, Q, F, n_iter=1, filter_acc_ix=None, filter_snp_ix=None, update_q=True, update_f=True):
+        """(Q, F, loglik) after ``n_iter`` joint EM iterations of the admixture model on the listed accessions over the listed DB
+        rows, made on the resident panel (``engine.admix``).  ``Q``: fp64 [n, K]; ``F``: fp64 [rows, K]; ``filter_acc_ix`` /
+        ``filter_snp_ix`` as for ``gram``."""
+        from .. import engine
+        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
+        return engine.admix(_resident_panel(self, "the admixture model needs"), Q, F, n_iter, filter_acc_ix, rows, update_q, update_f)
+
     def sim_counts(self, grp_off, err_rate, seed, filter_acc_ix=None, filter_snp_ix=None):
         """(score, ninfo) int32 [n_grp, n, n] of the sample simulated from every listed accession (its calls at the listed DB rows,
         errors at ``err_rate`` injected under ``seed``) against every listed accession, per group of the listed rows as ``grp_off``

@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_MK_P, PK_MK_G, PK_MK_K, PK_MK_U, PK_PCA_G, PK_PCA_F, PK_PCA_L, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs", "mk_planes", "mk_gain", "mk_pick", "mk_update", "pca_gram", "pca_fold", "pca_load"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_MK_P, PK_MK_G, PK_MK_K, PK_MK_U, PK_PCA_G, PK_PCA_F, PK_PCA_L, PK_ADM_R, PK_ADM_C, PK_ADM_F, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs", "mk_planes", "mk_gain", "mk_pick", "mk_update", "pca_gram", "pca_fold", "pca_load", "adm_rows", "adm_cols", "adm_fold"};
 
 struct Buf {
     void *p = nullptr;
@@ -78,6 +78,8 @@ struct Buf {
     X(ws_mk_planes) X(ws_mk_ut) X(ws_mk_need) X(ws_mk_gain) X(ws_mk_best) X(ws_mk_elig) X(ws_mk_coord) X(ws_mk_chosen) X(ws_mk_state) X(ws_mk_cols) \
     /* snpm_panel_gram / snpm_panel_loadings (snpm_api_pca.hpp): bit-planes [4][cols_pad][W] and table rows of a slab; partials [splits][tile pairs][64][64]; the matrix; column list; vec; loadings of a slab */ \
     X(ws_pca_planes) X(ws_pca_tab) X(ws_pca_part) X(ws_pca_out) X(ws_pca_cols) X(ws_pca_vec) X(ws_pca_load)                       \
+    /* snpm_panel_admix (snpm_api_adm.hpp): Q and Q' [2][ncols][KT]; F and F' [2][n_rows][KT]; partials [splits][ncols][KT]; the two buffers of the likelihood tree; loglik [n_iter]; column list */ \
+    X(ws_adm_q) X(ws_adm_f) X(ws_adm_part) X(ws_adm_ll) X(ws_adm_out) X(ws_adm_cols)                                              \
     /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
     /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
     X(ws_rows)                                                                                                                    \
@@ -698,6 +700,7 @@ int snpm_synchronize(snpm_ctx *ctx)
 #include "snpm_api_mk.hpp"
 
 #include "snpm_api_pca.hpp"
+#include "snpm_api_adm.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

@@ -925,6 +925,41 @@ def loadings(panel, tab, vec, cols=None, rows=None):
     return out
 
 
+ADMIX_MAX_K = 16               # SNPM_ADMIX_MAX_K: components of one ``admix`` call
+ADMIX_EPS = 1e-6               # SNPM_ADMIX_EPS: F stays inside [EPS, 1 - EPS]
+ADMIX_UPDATE_F, ADMIX_UPDATE_Q = 1, 2
+ADMIX_MAX_ITER = 10000         # iterations of one call
+
+
+def admix(panel, Q, F, n_iter=1, cols=None, rows=None, update_q=True, update_f=True):
+    """``n_iter`` joint EM iterations of the admixture model (STRUCTURE / FRAPPE / ADMIXTURE) on the accession columns of a resident
+    panel in one device call (``snpm_panel_admix``).  ``Q``: fp64 [n_cols, K], the ancestry of every listed column, entries >= 0, rows
+    summing to 1; ``F``: fp64 [n_rows, K], the alt frequency of every component at every selected row, inside [1e-6, 1 - 1e-6]; 1 <= K
+    <= 16; ``cols`` / ``rows`` as for ``gram``.  Dosage 0 / 2 / 1 for ref / alt / het; a missing call and an int8 panel's "other"
+    code contribute nothing.  Every iteration makes (Q', F') from the old pair, so the log-likelihood never decreases.  Returns
+    (Q, F, loglik): new arrays -- the inputs are not written -- and fp64 [n_iter], ``loglik[t]`` the likelihood of the parameters at
+    the START of iteration t.  With ``update_q=False`` / ``update_f=False`` that component comes back with its bits; with both False
+    the call only evaluates the likelihood.  fp64 throughout in an order fixed by the arguments: the same call returns the same bits.
+    Group (accession-sharded) and streamed panels are refused."""
+    _need_resident_panel(panel, "admix")
+    ctx = panel.ctx
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    row_idx, row0, n_rows = _row_selection(panel, rows)
+    Q, F = np.array(Q, dtype=np.float64, order="C"), np.array(F, dtype=np.float64, order="C")      # (copies: the call writes them)
+    assert Q.ndim == 2 and Q.shape[0] == ncols, "Q is [n_cols, K]: got %r for %d columns" % (Q.shape, ncols)
+    K = Q.shape[1]
+    assert F.shape == (n_rows, K), "F is [n_rows, K]: got %r for %d rows and K = %d" % (F.shape, n_rows, K)
+    n_iter = int(n_iter)
+    loglik = np.zeros(max(n_iter, 0), dtype=np.float64)
+    flags = (ADMIX_UPDATE_F if update_f else 0) | (ADMIX_UPDATE_Q if update_q else 0)
+    check(ctx.lib.snpm_panel_admix(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, K, n_iter, flags, ptr(Q), ptr(F), ptr(loglik)), ctx.h)
+    return Q, F, loglik
+
+
 MK_MAX_ACCESSIONS = 4096       # SNPM_MK_MAX_ACCESSIONS: columns of one ``marker_select`` call
 MK_NO_LIMIT = 2 ** 62           # ``max_markers=None``
 MK_STOP_REASONS = ("all pairs resolved", "max_markers reached", "no eligible row with gain")
