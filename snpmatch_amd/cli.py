@@ -1,21 +1,24 @@
 """
-Command line: ``snpmatch inbred``, ``snpmatch cross`` and ``snpmatch genotype_cross`` with the reference's flags
-(snpmatch/__init__.py:44-78), logging setup (:23-34) and exit codes (:155-183), plus ``makedb-native``
-to write the flat panel format this engine streams to the GPU.  ``genotype_cross`` serves the windowed likelihood-ratio
-mode with the parents named as two accessions of the database (``-p 6091x6191``); the HMM genotyper of the reference's
-``--hmm`` flag is the subcommand ``genotype_cross_hmm``.  ``--hmm`` itself and ``-q / --father`` are refused with a message
-(core/genotype_cross.py says why).  ``pairsnp`` compares two sample files as the reference does; ``pairsnp-batch`` compares every
-pair of a cohort in one device call.  ``kinship`` (not in the reference as a command) counts the relatedness of every pair of
-accessions of the database on the device and lists the near-identical ones; ``sitestats`` (not in the reference as a command
-either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter; ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of
-neighbouring DB rows inside a band on the device and prunes the rows by it; ``windows`` (not in the reference as a command) counts, per genome window, the
-heterozygosity of every accession and the mismatch of listed pairs of accessions on the device; ``f1search`` (not in the reference) scores
-the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles; ``parentsearch`` (not in the reference)
-scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third; ``simulate`` draws a test sample from the database as the reference does (host only,
-the same draws under one ``--seed``); ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker
-counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses; ``mosaic`` (not in the reference) paints a sample of more than two
-sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state; ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments; ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused; ``pca`` (not in the reference) makes the genotype relationship matrix of the accessions on the device (an fp64 rank-R update, every row weighted by its allele frequency), decomposes it and projects samples onto its principal axes: which part of the collection a sample that matches no accession belongs to; ``admixture`` (not in the reference) fits the admixture model of STRUCTURE / ADMIXTURE -- every accession a mixture of K ancestral populations -- by joint EM on the device, the parameters resident between iterations, and writes the population file the other panel commands take as ``--pops``.  The other reference subcommands (parser, makedb) are outside the accelerated
-path.
+Command line, one subcommand (or group of them) per line:
+
+  * ``snpmatch inbred``, ``snpmatch cross`` and ``snpmatch genotype_cross`` with the reference's flags (snpmatch/__init__.py:44-78), logging setup (:23-34) and exit codes (:155-183), plus ``makedb-native`` to write the flat panel format this engine streams to the GPU.
+  * ``genotype_cross`` serves the windowed likelihood-ratio mode with the parents named as two accessions of the database (``-p 6091x6191``); the HMM genotyper of the reference's ``--hmm`` flag is the subcommand ``genotype_cross_hmm``.  ``--hmm`` itself and ``-q / --father`` are refused with a message (core/genotype_cross.py says why).
+  * ``pairsnp`` compares two sample files as the reference does; ``pairsnp-batch`` compares every pair of a cohort in one device call.
+  * ``kinship`` (not in the reference as a command) counts the relatedness of every pair of accessions of the database on the device and lists the near-identical ones.
+  * ``sitestats`` (not in the reference as a command either) counts the alleles of every DB row per population on the device and writes frequencies, missingness and a site filter.
+  * ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of neighbouring DB rows inside a band on the device and prunes the rows by it.
+  * ``windows`` (not in the reference as a command) counts, per genome window, the heterozygosity of every accession and the mismatch of listed pairs of accessions on the device.
+  * ``f1search`` (not in the reference) scores the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles.
+  * ``parentsearch`` (not in the reference) scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third.
+  * ``simulate`` draws a test sample from the database as the reference does (host only, the same draws under one ``--seed``).
+  * ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses.
+  * ``mosaic`` (not in the reference) paints a sample of more than two sources -- a MAGIC line, a multi-parent RIL, an admixed sample -- as a mosaic of the accessions of the database on the device: the copying-model Viterbi path with a uniform switch cost, every accession a state.
+  * ``ibd`` (not in the reference) finds, for EVERY pair of accessions of the database, the genome windows in which the two are identical and the runs of such windows along each chromosome: shared haplotype segments.
+  * ``markers`` (not in the reference) chooses a small set of SNPs that separates EVERY pair of accessions of the database on the device -- the greedy set cover, round by round inside one device call: the SNPs to genotype so that no two accessions are confused.
+  * ``pca`` (not in the reference) makes the genotype relationship matrix of the accessions on the device (an fp64 rank-R update, every row weighted by its allele frequency), decomposes it and projects samples onto its principal axes: which part of the collection a sample that matches no accession belongs to.
+  * ``admixture`` (not in the reference) fits the admixture model of STRUCTURE / ADMIXTURE -- every accession a mixture of K ancestral populations -- by joint EM on the device, the parameters resident between iterations, and writes the population file the other panel commands take as ``--pops``.
+
+The other reference subcommands (parser, makedb) are outside the accelerated path.
 """
 import argparse
 import logging
@@ -46,6 +49,15 @@ def check_file(inFile):
         die("file: %s not specified" % inFile)
     if not os.path.exists(inFile):
         die("input file does not exist: " + inFile)
+
+
+def check_files(args, required=(), optional=()):
+    """``check_file`` on the files a subcommand needs and on those of its optional files that are given"""
+    for key in required:
+        check_file(args[key])
+    for key in optional:
+        if args.get(key):
+            check_file(args[key])
 
 
 def snpmatch_inbred(args):
@@ -103,54 +115,37 @@ def snpmatch_pair_cohort(args):
 
 def snpmatch_kinship(args):
     from .core import kinship
-    check_file(args['hdf5File'])
-    if args['accFile']:
-        check_file(args['accFile'])
+    check_files(args, ('hdf5File',), ('accFile',))
     kinship.potatoKinship(args)
 
 
 def snpmatch_sitestats(args):
     from .core import sitestats
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'popFile'):
-        if args[key]:
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'popFile'))
     sitestats.potatoSiteStats(args)
 
 
 def snpmatch_ld(args):
     from .core import ld
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'sitesFile'):
-        if args[key]:
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'sitesFile'))
     ld.potatoLD(args)
 
 
 def snpmatch_windows(args):
     from .core import windows
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'pairsFile'):
-        if args[key]:
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'pairsFile'))
     windows.potatoWindows(args)
 
 
 def snpmatch_f1search(args):
     from .core import f1search
-    check_file(args['inFile'])
-    check_file(args['hdf5File'])
-    if args['accFile']:
-        check_file(args['accFile'])
+    check_files(args, ('inFile', 'hdf5File'), ('accFile',))
     f1search.potatoF1Search(args)
 
 
 def snpmatch_parentsearch(args):
     from .core import parentsearch
-    check_file(args['inFile'])
-    check_file(args['hdf5File'])
-    if args['accFile']:
-        check_file(args['accFile'])
+    check_files(args, ('inFile', 'hdf5File'), ('accFile',))
     parentsearch.potatoParentSearch(args)
 
 
@@ -166,54 +161,37 @@ def snpmatch_simulate(args):
 
 def snpmatch_power(args):
     from .core import power
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'sitesFile'):
-        if args.get(key):
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'sitesFile'))
     power.potatoPower(args)
 
 
 def snpmatch_mosaic(args):
     from .core import mosaic
-    check_file(args['inFile'])
-    check_file(args['hdf5File'])
-    if args['accFile']:
-        check_file(args['accFile'])
+    check_files(args, ('inFile', 'hdf5File'), ('accFile',))
     mosaic.potatoMosaic(args)
 
 
 def snpmatch_ibd(args):
     from .core import ibd
-    check_file(args['hdf5File'])
-    if args['accFile']:
-        check_file(args['accFile'])
+    check_files(args, ('hdf5File',), ('accFile',))
     ibd.potatoIBD(args)
 
 
 def snpmatch_markers(args):
     from .core import markers
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'sitesFile'):
-        if args[key]:
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'sitesFile'))
     markers.potatoMarkers(args)
 
 
 def snpmatch_admixture(args):
     from .core import admixture
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'popFile', 'sitesFile', 'inFile'):
-        if args[key]:
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'popFile', 'sitesFile', 'inFile'))
     admixture.potatoAdmixture(args)
 
 
 def snpmatch_pca(args):
     from .core import pca
-    check_file(args['hdf5File'])
-    for key in ('accFile', 'popFile', 'sitesFile', 'inFile'):
-        if args[key]:
-            check_file(args[key])
+    check_files(args, ('hdf5File',), ('accFile', 'popFile', 'sitesFile', 'inFile'))
     pca.potatoPCA(args)
 
 
@@ -229,6 +207,13 @@ def get_options(description, version_message):
     p.add_argument('-V', '--version', action='version', version=version_message)
     sub = p.add_subparsers(title='subcommands', description='Choose a command to run', help='Following commands are supported')
 
+    def db_options(sp, required=True):
+        sp.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File", required=required, help="Path to SNP matrix (as for inbred)")
+        sp.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+
+    def verbose(sp):
+        sp.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+
     def common(sp, default_out):
         sp.add_argument("-i", "--input_file", dest="inFile", help="VCF/BED file for the variants in the sample")
         sp.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File",
@@ -237,7 +222,7 @@ def get_options(description, version_message):
                         help="Path to SNP matrix chunked column-wise (optional for flat panels)")
         sp.add_argument("--skip_db_hets", action="store_true", dest="skip_db_hets", default=False,
                         help="Replace heterozygous calls in DB with nan during the analysis.")
-        sp.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+        verbose(sp)
         sp.add_argument("-o", "--output", dest="outFile", default=default_out, help="Output file prefix")
 
     inbred = sub.add_parser('inbred', help="SNPmatch on the inbred samples")
@@ -248,11 +233,10 @@ def get_options(description, version_message):
     # not in the reference (which starts a process, and opens the DB, per sample): many samples against ONE resident DB
     batch = sub.add_parser('inbred-batch', help="`inbred` for many samples: the DB is loaded once, samples are scored a batch per device call")
     batch.add_argument("-i", "--input_files", dest="inFiles", nargs='+', required=True, help="VCF/BED files, one sample each")
-    batch.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File", help="Path to SNP matrix (as for inbred)")
-    batch.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(batch, required=False)
     batch.add_argument("--skip_db_hets", action="store_true", dest="skip_db_hets", default=False,
                        help="Replace heterozygous calls in DB with nan during the analysis.")
-    batch.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(batch)
     batch.add_argument("-o", "--output", dest="outFile", default="identify_inbred",
                        help="Output prefix: sample <name>.vcf writes <prefix>.<name>.scores.txt / .matches.json")
     batch.add_argument("--batch_size", dest="batchSize", default=64, type=int, help="samples per device call")
@@ -282,7 +266,7 @@ def get_options(description, version_message):
     gcross.add_argument("--good_samples", dest="good_samples", default=None, help="accepted and unused, as in the reference's own call path")
     gcross.add_argument("--hmm", action="store_true", dest="hmm", default=False, help="(refused) the reference's HMM genotyper")
     gcross.add_argument("-o", "--output", dest="outFile", default="genotype_cross", help="output file")
-    gcross.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(gcross)
     gcross.set_defaults(func=snpmatch_genotype_cross)
 
     ghmm = sub.add_parser('genotype_cross_hmm', help="Genotype F2 individuals of a cross marker by marker (AA / AB / BB) with a 3-state HMM")
@@ -295,7 +279,7 @@ def get_options(description, version_message):
     ghmm.add_argument("--genome", dest="genome", default="athaliana_tair10",
                       help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen, optionally recomb_rates)")
     ghmm.add_argument("-o", "--output", dest="outFile", default="genotype_cross_hmm", help="output file")
-    ghmm.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(ghmm)
     ghmm.set_defaults(func=snpmatch_genotype_cross_hmm)
 
     pair = sub.add_parser('pairsnp', help="pairwise comparison of two snp files")
@@ -303,7 +287,7 @@ def get_options(description, version_message):
     pair.add_argument("-j", "--input_file_2", dest="inFile_2", help="VCF/BED file for the variants in the sample two")
     pair.add_argument("-d", "--hdf5_file", dest="hdf5File", default=None,
                       help="Path to SNP matrix (as for inbred): only positions the database holds are compared")
-    pair.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(pair)
     pair.add_argument("-o", "--output", dest="outFile", default="pairsnp", help="output json file")
     pair.set_defaults(func=snpmatch_paircomparions)
 
@@ -313,28 +297,26 @@ def get_options(description, version_message):
                        help="one multi-sample VCF, or VCF/BED files of one sample each")
     pairs.add_argument("-d", "--hdf5_file", dest="hdf5File", default=None,
                        help="Path to SNP matrix (as for inbred): only positions the database holds are compared")
-    pairs.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(pairs)
     pairs.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pairs.tsv and <prefix>.pairs.npz")
     pairs.set_defaults(func=snpmatch_pair_cohort)
 
     # not in the reference as a command (its Genotype.kinship_given_snps is a method): relatedness of every pair of accessions of the DB
     kin = sub.add_parser('kinship', help="kinship of every pair of accessions of the database, and the list of near-identical pairs")
-    kin.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    kin.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(kin)
     kin.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     kin.add_argument("--bed", dest="bed", default=None, help="only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
     kin.add_argument("--min_identity", dest="min_identity", default=0.99, type=float,
                      help="list a pair as duplicates from this share of equal calls among the rows where both are homozygous (default 0.99)")
     kin.add_argument("--min_sites", dest="min_sites", default=100, type=int,
                      help="... and only when both are homozygous at this many rows or more (default 100)")
-    kin.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(kin)
     kin.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.kinship.npz and <prefix>.duplicates.tsv")
     kin.set_defaults(func=snpmatch_kinship)
 
     # not in the reference as a command (its Genotype.get_af_snps is a method): allele counts and frequencies of every DB row per population
     site = sub.add_parser('sitestats', help="allele counts, frequencies and missingness of every SNP of the database, per population")
-    site.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    site.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(site)
     site.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line: one population of these (default: all accessions)")
     site.add_argument("--pops", dest="popFile", default=None, help="text file of two columns, accession and population (# lines are skipped): statistics per population")
     site.add_argument("--bed", dest="bed", default=None, help="only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
@@ -343,14 +325,13 @@ def get_options(description, version_message):
     site.add_argument("--min_maf", dest="min_maf", default=None, type=float, help="write <prefix>.sites.tsv: rows whose maf is at least this in every population")
     site.add_argument("--max_missing", dest="max_missing", default=None, type=float,
                       help="write <prefix>.sites.tsv: rows whose share of accessions without a call is at most this in every population")
-    site.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(site)
     site.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.sitestats.npz, <prefix>.sitestats.json and, with a threshold, <prefix>.sites.tsv")
     site.set_defaults(func=snpmatch_sitestats)
 
     # not in the reference as a command (its calculate_ld does not run): LD between neighbouring SNPs of the DB and pruning of a marker set by it
     ldp = sub.add_parser('ld', help="linkage disequilibrium (r2) of every SNP with the SNPs after it inside a band, the decay curve, and LD pruning of the rows")
-    ldp.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    ldp.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(ldp)
     ldp.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     ldp.add_argument("--bed", dest="bed", default=None, help="only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
     ldp.add_argument("--sites", dest="sitesFile", default=None, help="only the rows listed in a <prefix>.sites.tsv of sitestats (columns chr and pos)")
@@ -359,55 +340,51 @@ def get_options(description, version_message):
     ldp.add_argument("--r2", dest="r2", default=0.2, type=float, help="prune a row whose r2 with an earlier kept row of the band exceeds this (default 0.2)")
     ldp.add_argument("--min_n", dest="min_n", default=2, type=int, help="r2 is undefined with fewer accessions informative at both rows (default 2)")
     ldp.add_argument("--keep_r2", action="store_true", dest="keep_r2", default=False, help="also write <prefix>.ld.npz: chr, pos, r2 [rows, band], keep")
-    ldp.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(ldp)
     ldp.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pruned.tsv and <prefix>.ld.json")
     ldp.set_defaults(func=snpmatch_ld)
 
     # not in the reference as a command (it has the two methods): per genome window, heterozygosity of the accessions and mismatch of pairs
     win = sub.add_parser('windows', help="per genome window: heterozygosity of every accession of the DB and mismatch of listed pairs of accessions (e.g. the duplicates of kinship)")
-    win.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    win.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(win)
     win.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     win.add_argument("--pairs", dest="pairsFile", default=None, help="text file whose first two columns name pairs of the selected accessions (a <prefix>.duplicates.tsv of kinship goes straight in)")
     win.add_argument("--pairs_only", action="store_true", dest="pairs_only", default=False, help="take the members of the pairs as the accessions")
     win.add_argument("--genome", dest="genome", default="athaliana_tair10", help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
     win.add_argument("-b", "--window_size", dest="binLen", default=300000, type=int, help="window length in bp (default 300000)")
     win.add_argument("--min_sites", dest="min_sites", default=5, type=int, help="a window is judged with MORE than this many informative rows; het is nan otherwise (default 5, the reference's)")
-    win.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(win)
     win.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.windows.npz, <prefix>.het_windows.tsv, <prefix>.windows.json and, with --pairs, <prefix>.pair_windows.tsv")
     win.set_defaults(func=snpmatch_windows)
 
     # not in the reference (its match_insilico_f1s crosses the ten best single accessions): the in-silico F1 of every pair of accessions
     f1s = sub.add_parser('f1search', help="parents of an F1 sample: the in-silico F1 of EVERY pair of accessions of the database scored against the sample")
     f1s.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF/BED file for the variants in the sample")
-    f1s.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    f1s.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(f1s)
     f1s.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession name per line (default: all accessions)")
     f1s.add_argument("--top", dest="top", default=10, type=int, help="pairs of the shortlist, re-scored with the sample's weights (default 10, at most 16)")
     f1s.add_argument("--min_sites", dest="min_sites", default=100, type=int, help="a pair is ranked only with this many informative rows or more (default 100)")
-    f1s.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(f1s)
     f1s.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.f1search.scores.txt, <prefix>.f1search.npz and <prefix>.f1search.json")
     f1s.set_defaults(func=snpmatch_f1search)
 
     # not in the reference (its cross guesses the parents of an F2 from the single accessions that win clean windows): every pair per window
     par = sub.add_parser('parentsearch', help="parents of a recombinant sample (F2, backcross): EVERY pair of accessions of the database scored per genome window as parent A, parent B or their F1")
     par.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF/BED file for the variants in the sample")
-    par.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    par.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(par)
     par.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession name per line (default: all accessions)")
     par.add_argument("--genome", dest="genome", default="athaliana_tair10", help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
     par.add_argument("-b", "--binLength", dest="binLen", default=300000, type=int, help="window length in bp (default 300000)")
     par.add_argument("--top", dest="top", default=10, type=int, help="pairs of the shortlist, with their window tracks (default 10, at most 16)")
     par.add_argument("--min_sites", dest="min_sites", default=100, type=int, help="a pair is ranked only with this many rows or more in its used windows (default 100)")
     par.add_argument("--min_win_sites", dest="min_win_sites", default=5, type=int, help="a window is used for a pair only with this many informative rows or more (default 5)")
-    par.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(par)
     par.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.parentsearch.json, <prefix>.parentsearch.npz and <prefix>.parentsearch.windows.tsv")
     par.set_defaults(func=snpmatch_parentsearch)
 
     # the reference's command, host only: the same draws as the reference under one seed
     sim = sub.add_parser('simulate', help="Given SNP database, check the genotyping efficiency randomly selecting 'n' number of SNPs")
-    sim.add_argument("-d", "--hdf5_file", default=None, dest="hdf5File", help="Path to SNP matrix (as for inbred)")
-    sim.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(sim, required=False)
     sim.add_argument("-a", "--ecotype_id", dest="AccID", help="Ecotype ID you want draw the SNPs")
     sim.add_argument("-n", "--number_of_snps", dest="numSNPs", help="number of SNPs to draw in random to genotype the sample", type=int)
     sim.add_argument("-p", "--error_rate", dest="err_rate", default=0.001, type=float,
@@ -417,13 +394,12 @@ def get_options(description, version_message):
                      help="for F1s: the probability that a segregating site stays heterozygous; the rest become homozygous ref or alt, half each")
     sim.add_argument("--seed", dest="seed", default=None, type=int, help="np.random.seed before the draws (not in the reference): the same sample again")
     sim.add_argument("-o", "--output", dest="outFile", help="Output BED file: chromosome, position, genotype")
-    sim.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(sim)
     sim.set_defaults(func=snpmatch_simulate)
 
     # not in the reference (simulate + inbred, one accession and one n at a time): every accession simulated and scored against every accession
     pw = sub.add_parser('power', help="identifiability of every accession of the database: with n random SNPs and a call error rate, whom does inbred identify uniquely, whom does it confuse")
-    pw.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    pw.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(pw)
     pw.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     pw.add_argument("--bed", dest="bed", default=None, help="draw the markers from the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
     pw.add_argument("--sites", dest="sitesFile", default=None, help="draw the markers from the listed rows only: a file with the columns chr and pos (a <prefix>.sites.tsv of sitestats, a <prefix>.markers.tsv of markers)")
@@ -432,55 +408,51 @@ def get_options(description, version_message):
     pw.add_argument("--trials", dest="trials", default=3, type=int, help="marker ladders drawn, one device call each (default 3)")
     pw.add_argument("--seed", dest="seed", default=1, type=int, help="seed of the ladders and of the injected errors (default 1)")
     pw.add_argument("--lr_thres", dest="lr_thres", default=3.841, type=float, help="an accession is ambiguous with the top hit below this likelihood ratio (default 3.841, as inbred)")
-    pw.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(pw)
     pw.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.power.tsv, <prefix>.power.json and <prefix>.power.npz")
     pw.set_defaults(func=snpmatch_power)
 
     # not in the reference: a sample of more than two sources (MAGIC lines, multi-parent RILs, admixed samples) painted accession by accession
     mos = sub.add_parser('mosaic', help="paint every sample of the input as a mosaic of the accessions of the database: which accession it copies at every matched SNP (copying-model Viterbi with a uniform switch cost)")
     mos.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF/BED file of the sample; a multi-sample VCF is painted as a batch on its shared records")
-    mos.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    mos.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(mos)
     mos.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession (founder) name per line (default: all accessions)")
     mos.add_argument("--switch_cost", dest="switch_cost", default=40, type=int, help="cost of a change of accession, 1 .. 1048576 (default 40)")
     mos.add_argument("--mismatch", dest="mismatch", default=2, type=int, help="cost of a homozygous call against the other homozygous call, or against the DB's 'other' code, 0 .. 15 (default 2)")
     mos.add_argument("--het_cost", dest="het_cost", default=1, type=int, help="cost of a heterozygous call against a homozygous one, either way, 0 .. 15 (default 1)")
     mos.add_argument("--min_seg_sites", dest="min_seg_sites", default=20, type=int, help="segments of fewer sites are flagged in the segment table (default 20)")
-    mos.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(mos)
     mos.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.mosaic.segments.tsv, <prefix>.mosaic.json and <prefix>.mosaic.npz")
     mos.set_defaults(func=snpmatch_mosaic)
 
     # not in the reference: where along the genome every pair of accessions is identical (shared haplotype segments)
     ibd = sub.add_parser('ibd', help="shared segments (identity by descent): for EVERY pair of accessions of the database the genome windows in which the two are identical, and the runs of such windows along each chromosome")
-    ibd.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    ibd.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(ibd)
     ibd.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     ibd.add_argument("--genome", dest="genome", default="athaliana_tair10", help="Genome id or path to a reference JSON file (ref_chrs, ref_chrlen)")
     ibd.add_argument("-b", "--window_size", dest="binLen", default=100000, type=int, help="window length in bp (default 100000)")
     ibd.add_argument("--min_win_sites", dest="min_win_sites", default=20, type=int, help="a window is used for a pair only with this many rows or more at which both accessions are homozygous (default 20)")
     ibd.add_argument("--max_diff", dest="max_diff", default=0.001, type=float, help="a used window is shared when at most this fraction of those rows differ, 0 .. 1 (default 0.001)")
     ibd.add_argument("--min_run", dest="min_run", default=5, type=int, help="a run is reported with this many shared windows or more (default 5)")
-    ibd.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(ibd)
     ibd.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.ibd.npz, <prefix>.ibd.pairs.tsv, <prefix>.ibd.segments.tsv and <prefix>.ibd.json")
     ibd.set_defaults(func=snpmatch_ibd)
 
     # not in the reference: a small set of SNPs that separates every pair of accessions (the step after power)
     mks = sub.add_parser('markers', help="a minimal marker set: SNPs chosen greedily so that every pair of accessions of the database differs at --depth of them (homozygous calls only); greedy set cover, not optimal")
-    mks.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    mks.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(mks)
     mks.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     mks.add_argument("--bed", dest="bed", default=None, help="candidates: only the DB rows of a region: Chr1,1,1000000 (default: all rows)")
     mks.add_argument("--sites", dest="sitesFile", default=None, help="candidates: only the rows listed in a <prefix>.sites.tsv of sitestats or a <prefix>.pruned.tsv of ld (columns chr and pos)")
     mks.add_argument("--depth", dest="depth", default=1, type=int, help="every pair must differ at this many chosen SNPs, 1 .. 255 (default 1)")
     mks.add_argument("--max_markers", dest="max_markers", default=None, type=int, help="stop after this many SNPs (default: no limit)")
     mks.add_argument("--min_dist_bp", dest="min_dist_bp", default=0, type=int, help="a chosen SNP excludes every candidate closer than this on its chromosome (default 0: no exclusion)")
-    mks.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(mks)
     mks.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.markers.tsv, <prefix>.markers.json and <prefix>.markers.npz")
     mks.set_defaults(func=snpmatch_markers)
 
     pc = sub.add_parser('pca', help="population structure of the database: the genotype relationship matrix of its accessions and its principal components; with -i, samples projected onto them")
-    pc.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    pc.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(pc)
     pc.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     pc.add_argument("--pops", dest="popFile", default=None, help="text file, accession and population per line: the union of the populations is analysed, every output row carries its population")
     pc.add_argument("--bed", dest="bed", default=None, help="use the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
@@ -490,13 +462,12 @@ def get_options(description, version_message):
     pc.add_argument("--components", dest="components", default=10, type=int, help="principal components to report, 1 .. min(32, accessions) (default 10)")
     pc.add_argument("--keep_grm", action="store_true", dest="keep_grm", default=False, help="store the relationship matrix in <prefix>.pca.npz")
     pc.add_argument("-i", "--input_file", dest="inFile", default=None, help="samples to project: a VCF (every sample column) or a BED file")
-    pc.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(pc)
     pc.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.pca.tsv, <prefix>.pca.npz, <prefix>.pca.json and, with -i, <prefix>.projection.tsv")
     pc.set_defaults(func=snpmatch_pca)
 
     ad = sub.add_parser('admixture', help="ancestry proportions of every accession of the database under the admixture model (K ancestral populations), fitted by EM on the device; writes a --pops file for sitestats / ld / pca; with -i, the proportions of samples")
-    ad.add_argument("-d", "--hdf5_file", dest="hdf5File", required=True, help="Path to SNP matrix (as for inbred)")
-    ad.add_argument("-e", "--hdf5_acc_file", default=None, dest="hdf5accFile", help="Path to SNP matrix chunked column-wise (optional for flat panels)")
+    db_options(ad)
     ad.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one accession name per line (default: all accessions)")
     ad.add_argument("--pops", dest="popFile", default=None, help="text file, accession and population per line: the union of the populations is analysed, the outputs compare the clusters with them")
     ad.add_argument("--bed", dest="bed", default=None, help="use the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
@@ -509,7 +480,7 @@ def get_options(description, version_message):
     ad.add_argument("--max_iter", dest="max_iter", default=2000, type=int, help="EM iterations per restart, at most (default 2000)")
     ad.add_argument("--tol", dest="tol", default=1e-7, type=float, help="stop when an iteration gains less than this fraction of the log-likelihood (default 1e-7)")
     ad.add_argument("-i", "--input_file", dest="inFile", default=None, help="samples to place: a VCF (every sample column) or a BED file")
-    ad.add_argument("-v", "--verbose", action="store_true", dest="logDebug", default=False, help="Show verbose debugging output")
+    verbose(ad)
     ad.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.admixture.Q.tsv, .admixture.pops.tsv, .admixture.npz, .admixture.json and, with -i, <prefix>.ancestry.tsv")
     ad.set_defaults(func=snpmatch_admixture)
 

@@ -37,8 +37,7 @@ import logging
 
 import numpy as np
 
-from . import f1search, pca, sitestats, snp_genotype
-from .ld import read_sites, rows_of_sites
+from . import _select, pca, snp_genotype
 
 log = logging.getLogger(__name__)
 
@@ -135,7 +134,7 @@ def sample_classes(g, used, samples, chrs, pos, gt):
     hit = at >= 0
     classes = np.full((len(samples), len(used)), NO_CLASS, dtype=np.uint8)
     for s in range(len(samples)):
-        classes[s, at[hit]] = f1search.hard_classes(gt[:, s])[rec_rows[hit]]
+        classes[s, at[hit]] = _select.hard_classes(gt[:, s])[rec_rows[hit]]
     return classes
 
 
@@ -192,8 +191,7 @@ def analyse(g, acc_ix, n_acc, rows, min_maf, max_missing, K, seed=1, restarts=1,
 
 def potatoAdmixture(args):
     """entry point of ``snpmatch admixture``"""
-    if args.get('bed') and args.get('sitesFile'):
-        raise ValueError("give either --bed or --sites, not both")
+    _select.one_row_option(args)
     given = lambda key, default: default if args.get(key) is None else args[key]      # noqa: E731
     min_maf, max_missing, K = float(given('min_maf', 0.05)), float(given('max_missing', 0.1)), int(args['K'])
     seed, restarts, max_iter, tol = int(given('seed', 1)), int(given('restarts', 1)), int(given('max_iter', 2000)), float(given('tol', 1e-7))
@@ -211,22 +209,16 @@ def potatoAdmixture(args):
         raise ValueError("the admixture model needs at least 2 accessions, got %d" % len(names))
     if K > len(names):
         raise ValueError("-K must not exceed the number of accessions: K = %d, %d accessions" % (K, len(names)))
-    if args.get('sitesFile'):
-        rows = rows_of_sites(g, *read_sites(args['sitesFile']))
-    elif args.get('bed'):
-        rows = np.asarray(g.determine_snp_ix_given_bed(args['bed']), dtype=np.int64)
-    else:
-        rows = np.arange(len(g.g.positions), dtype=np.int64)
+    rows = _select.rows_of(g, args)
     log.info("admixture: %d accessions, %d selected rows, K = %d", len(names), len(rows), K)
     res = analyse(g, acc_ix, len(names), rows, min_maf, max_missing, K, seed, restarts, max_iter, tol)
-    res["chr"], res["pos"] = sitestats.row_chromosomes(g, res["rows"]), np.asarray(g.g.positions)[res["rows"]].astype(np.int64)
+    res["chr"], res["pos"] = _select.row_chromosomes(g, res["rows"]), np.asarray(g.g.positions)[res["rows"]].astype(np.int64)
     settings = {"K": K, "min_maf": min_maf, "max_missing": max_missing, "seed": seed, "max_iter": max_iter, "tol": tol, "populations": pop_names,
                 "bed": args.get('bed'), "sites": args.get('sitesFile')}
     stats = write_outputs(args['outFile'], names, pop_of, pop_names, res, settings)
     log.info("%d of %d rows used; %d iterations, log-likelihood %.6f; cluster sizes %s", res["R"], len(rows), res["iterations"], res["loglik"], stats["cluster_sizes"])
     if args.get('inFile'):
-        from . import mosaic
-        samples, chrs, pos, gt = mosaic.read_samples(args['inFile'], args.get('logDebug', False))
+        samples, chrs, pos, gt = _select.read_samples(args['inFile'], args.get('logDebug', False))
         q, n_sites = sample_ancestry(sample_classes(g, res["rows"], samples, chrs, pos, gt), res["F"], max_iter, tol)
         write_ancestry(args['outFile'], samples, q, n_sites)
         stats["samples_placed"] = int(np.count_nonzero(n_sites > 0))

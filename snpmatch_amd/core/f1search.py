@@ -33,26 +33,15 @@ import logging
 
 import numpy as np
 
-from . import kinship, parsers, snp_genotype, snpmatch
+from . import _select, parsers, snp_genotype, snpmatch
+from ._select import hard_classes  # noqa: F401  (the name tests and tools import)
 
 log = logging.getLogger(__name__)
 
 TOP = 10                    # default of --top: pairs of the shortlist
 MAX_TOP = 16                # ... at most: the members of 16 pairs fit the 32 accessions of one snpm_query_f1_pairs call
 MIN_SITES = 100             # default of --min_sites: informative rows below which a pair is not ranked
-NO_CLASS = 0xFF
-
-
-def hard_classes(gt):
-    """The sample's class per entry of its GT column, uint8: 0 ref, 1 alt, 2 het, 0xFF none -- ``parseGT`` of the text, i.e. the
-    column in which the reference's ``ParseInputs.get_wei_from_GT`` puts its 1 (weights are [ref, het, alt]: class 1 is column 2,
-    class 2 column 1).  As there, the separator is the one of the FIRST entry, a text that is not recognised (``1/2``, the other
-    separator) counts as ref, and -1 (``./.``) -- or any other code of a purely numeric column -- has no class."""
-    codes = parsers.parseGT(np.asarray(gt))
-    out = np.full(len(codes), NO_CLASS, dtype=np.uint8)
-    known = (codes >= 0) & (codes <= 2)
-    out[known] = codes[known].astype(np.uint8)
-    return out
+NO_CLASS = _select.NO_CLASS
 
 
 def _better(p, q):
@@ -184,16 +173,7 @@ def potatoF1Search(args):
     inputs = snpmatch.parse_inputs_once(args['inFile'], args.get('logDebug', False))
     log.info("loading genotype files!")
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    acc_ix = None
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        acc_ix = np.array(found, dtype=np.int64)
+    acc_ix, _ = _select.accessions_of(g, args)
     search = F1Search(inputs, g, args['outFile'], top, min_sites, acc_ix)
     log.info("finished!")
     return search.stats

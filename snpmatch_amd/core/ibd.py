@@ -26,7 +26,7 @@ import logging
 
 import numpy as np
 
-from . import genomes, kinship, snp_genotype
+from . import _select, genomes, snp_genotype
 
 log = logging.getLogger(__name__)
 
@@ -144,16 +144,7 @@ def potatoIBD(args):
     max_diff_ppm = int(round(max_diff * 1e6))
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
     genome = genomes.Genome(given('genome', "athaliana_tair10"))
-    acc_ix, names = None, g.accessions.tolist()
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        acc_ix, names = np.array(found, dtype=np.int64), wanted
+    acc_ix, names = _select.accessions_of(g, args)
     log.info("ibd: windows of %d bp, %d accessions", bin_len, len(names))
     table, counts, bits = genome_ibd(g, genome, bin_len, min_win_sites, max_diff_ppm, min_run, acc_ix)
     settings = {"window_size": bin_len, "min_win_sites": min_win_sites, "max_diff": max_diff, "max_diff_ppm": max_diff_ppm, "min_run": min_run}

@@ -15,23 +15,13 @@ import logging
 
 import numpy as np
 
-from . import snp_genotype
+from . import _select, snp_genotype
+from ._select import read_accession_list  # noqa: F401  (the name tests and tools import)
 
 log = logging.getLogger(__name__)
 
 MIN_IDENTITY = 0.99         # default of --min_identity: homozygous identity from which a pair is listed as duplicates
 MIN_SITES = 100             # default of --min_sites: rows at which both accessions are homozygous, below which a pair is not judged
-
-
-def read_accession_list(path):
-    """accession names, one per line (text after the first blank or tab of a line is ignored; empty lines and # lines are skipped)"""
-    names = []
-    with open(path) as fh:
-        for line in fh:
-            line = line.strip()
-            if line and not line.startswith("#"):
-                names.append(line.split()[0])
-    return names
 
 
 def duplicate_pairs(names, ninfo, same, diff, min_identity=MIN_IDENTITY, min_sites=MIN_SITES):
@@ -65,17 +55,8 @@ def write_outputs(prefix, names, ninfo, same, diff, min_identity=MIN_IDENTITY, m
 
 def potatoKinship(args):
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    acc_ix, names = None, g.accessions.tolist()
-    if args.get('accFile'):
-        wanted = read_accession_list(args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        acc_ix, names = np.array(found, dtype=np.int64), wanted
-    snp_ix = g.determine_snp_ix_given_bed(args['bed']) if args.get('bed') else None
+    acc_ix, names = _select.accessions_of(g, args)
+    snp_ix = _select.rows_of(g, args) if args.get('bed') else None
     log.info("kinship of %d accessions over %s rows", len(names), "all" if snp_ix is None else len(snp_ix))
     ninfo, same, diff = g.kinship_counts(acc_ix, snp_ix)
     rows = write_outputs(args['outFile'], names, ninfo, same, diff, args.get('min_identity', MIN_IDENTITY), args.get('min_sites', MIN_SITES))

@@ -19,49 +19,10 @@ import logging
 
 import numpy as np
 
-from . import kinship, sitestats, snp_genotype
+from . import _select, snp_genotype
+from ._select import read_sites, rows_of_sites  # noqa: F401  (the names tests and tools import)
 
 log = logging.getLogger(__name__)
-
-
-def read_sites(path):
-    """(chromosome names, positions) of a ``<prefix>.sites.tsv`` as ``sitestats`` writes it: a header line that names the columns
-    ``chr`` and ``pos``, tab-separated rows"""
-    with open(path) as fh:
-        header = fh.readline().rstrip("\n").split("\t")
-        if "chr" not in header or "pos" not in header:
-            raise ValueError("%s: the header must name the columns chr and pos, got %r" % (path, header))
-        ci, pi = header.index("chr"), header.index("pos")
-        chrs, pos = [], []
-        for n, line in enumerate(fh, 2):
-            fields = line.rstrip("\n").split("\t")
-            if fields == [""]:
-                continue
-            if len(fields) <= max(ci, pi):
-                raise ValueError("%s line %d: expected %d columns, got %r" % (path, n, len(header), line))
-            chrs.append(fields[ci])
-            pos.append(int(fields[pi]))
-    return chrs, np.asarray(pos, dtype=np.int64)
-
-
-def rows_of_sites(g, chrs, pos):
-    """the DB rows of the listed sites, ascending; a site that is not in the database is an error"""
-    regions = np.asarray(g.g.chr_regions)
-    rows = np.zeros(len(pos), dtype=np.int64)
-    names = np.asarray(chrs)
-    for name in dict.fromkeys(chrs):
-        which = g.get_chr_ind(name)
-        if which is None:
-            raise ValueError("chromosome %s of the site list is not in the database" % name)
-        first, last = int(regions[which][0]), int(regions[which][1])
-        db_pos = np.asarray(g.g.positions[first:last])
-        mine = np.flatnonzero(names == name)
-        at = np.searchsorted(db_pos, pos[mine])
-        found = (at < len(db_pos)) & (db_pos[np.minimum(at, max(len(db_pos) - 1, 0))] == pos[mine]) if len(db_pos) else np.zeros(len(mine), dtype=bool)
-        if not found.all():
-            raise ValueError("sites not in the database: %s" % ", ".join("%s:%d" % (name, p) for p in pos[mine][~found][:10].tolist()))
-        rows[mine] = first + at
-    return np.unique(rows)
 
 
 def mask_window(r2, pos, window_bp):
@@ -75,8 +36,7 @@ def mask_window(r2, pos, window_bp):
 
 def potatoLD(args):
     from .. import engine
-    if args.get('bed') and args.get('sitesFile'):
-        raise ValueError("give either --bed or --sites, not both")
+    _select.one_row_option(args)
     given = lambda key, default: default if args.get(key) is None else args[key]      # noqa: E731
     band, min_n, threshold = int(given('band', 50)), int(given('min_n', 2)), float(given('r2', 0.2))
     if not 1 <= band <= engine.LD_MAX_BAND:
@@ -84,24 +44,8 @@ def potatoLD(args):
     if min_n < 1:
         raise ValueError("--min_n must be at least 1, got %d" % min_n)
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    accs = None
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        if len(set(found)) != len(found):
-            raise ValueError("the accession list %s names an accession twice" % args['accFile'])
-        accs = np.array(found, dtype=np.int64)
-    if args.get('sitesFile'):
-        rows = rows_of_sites(g, *read_sites(args['sitesFile']))
-    elif args.get('bed'):
-        rows = np.asarray(g.determine_snp_ix_given_bed(args['bed']), dtype=np.int64)
-    else:
-        rows = np.arange(len(g.g.positions), dtype=np.int64)
+    accs, _ = _select.accessions_of(g, args, distinct=True)
+    rows = _select.rows_of(g, args)
     positions = np.asarray(g.g.positions)
     total, defined = np.zeros(band, dtype=np.float64), np.zeros(band, dtype=np.int64)
     kept_rows, kept_flags, bands = [], [], []
@@ -122,7 +66,7 @@ def potatoLD(args):
             bands.append(r2)
     rows = np.concatenate(kept_rows) if kept_rows else np.zeros(0, dtype=np.int64)
     keep = np.concatenate(kept_flags) if kept_flags else np.zeros(0, dtype=bool)
-    chrs, pos = sitestats.row_chromosomes(g, rows), positions[rows].astype(np.int64)
+    chrs, pos = _select.row_chromosomes(g, rows), positions[rows].astype(np.int64)
     with open(args['outFile'] + ".pruned.tsv", "w") as out:
         out.write("chr\tpos\n")
         for r in np.flatnonzero(keep).tolist():

@@ -26,8 +26,7 @@ import logging
 
 import numpy as np
 
-from . import kinship, sitestats, snp_genotype
-from .ld import read_sites, rows_of_sites
+from . import _select, snp_genotype
 
 log = logging.getLogger(__name__)
 
@@ -77,8 +76,7 @@ def write_outputs(prefix, names, rows, chrs, pos, result, settings):
 
 def potatoMarkers(args):
     """entry point of ``snpmatch markers``"""
-    if args.get('bed') and args.get('sitesFile'):
-        raise ValueError("give either --bed or --sites, not both")
+    _select.one_row_option(args)
     given = lambda key, default: default if args.get(key) is None else args[key]      # noqa: E731
     depth, min_dist = int(given('depth', 1)), int(given('min_dist_bp', 0))
     max_markers = None if args.get('max_markers') is None else int(args['max_markers'])
@@ -89,28 +87,12 @@ def potatoMarkers(args):
     if max_markers is not None and max_markers < 1:
         raise ValueError("--max_markers must be at least 1, got %d" % max_markers)
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    acc_ix, names = None, g.accessions.tolist()
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        if len(set(found)) != len(found):
-            raise ValueError("the accession list %s names an accession twice" % args['accFile'])
-        acc_ix, names = np.array(found, dtype=np.int64), wanted
-    if args.get('sitesFile'):
-        rows = rows_of_sites(g, *read_sites(args['sitesFile']))
-    elif args.get('bed'):
-        rows = np.asarray(g.determine_snp_ix_given_bed(args['bed']), dtype=np.int64)
-    else:
-        rows = np.arange(len(g.g.positions), dtype=np.int64)
+    acc_ix, names = _select.accessions_of(g, args, distinct=True)
+    rows = _select.rows_of(g, args)
     coord = coordinates(g, rows, min_dist) if min_dist > 0 else None
     log.info("markers: %d accessions, %d candidate rows, depth %d", len(names), len(rows), depth)
     result = g.marker_select(depth, max_markers, coord, min_dist, None, acc_ix, rows)
-    chrs, pos = sitestats.row_chromosomes(g, rows), np.asarray(g.g.positions)[rows].astype(np.int64)
+    chrs, pos = _select.row_chromosomes(g, rows), np.asarray(g.g.positions)[rows].astype(np.int64)
     settings = {"depth": depth, "max_markers": max_markers, "min_dist_bp": min_dist}
     stats = write_outputs(args['outFile'], names, rows, chrs, pos, result, settings)
     log.info("%d markers, %d units of need left (%s), %d unresolved pairs", stats["markers"], stats["remaining"], stats["stop_reason_text"], stats["unresolved_pairs"])

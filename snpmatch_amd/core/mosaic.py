@@ -33,7 +33,8 @@ import logging
 
 import numpy as np
 
-from . import f1search, kinship, parsers, snp_genotype, snpmatch
+from . import _select, f1search, snp_genotype
+from ._select import read_samples  # noqa: F401  (the name tests and tools import)
 
 log = logging.getLogger(__name__)
 
@@ -188,16 +189,6 @@ class Mosaic(object):
         return self.stats
 
 
-def read_samples(inFile, logDebug=False):
-    """(samples, chrs, pos, gt [n_records, n_samples]) of the input: every sample column of a VCF, the one sample of any other file"""
-    if inFile.endswith(".vcf") or inFile.endswith(".vcf.gz"):
-        calls = parsers.import_vcf_file(inFile, logDebug, samples_to_load=None)
-        gt = np.asarray(calls['gt'])
-        return [str(s) for s in calls['samples']], np.asarray(calls['chr']), np.asarray(calls['pos']), gt.reshape(len(calls['pos']), -1)
-    inputs = snpmatch.parse_inputs_once(inFile, logDebug)
-    return [str(inFile).split("/")[-1]], inputs.chrs, inputs.pos, np.asarray(inputs.gt).reshape(-1, 1)
-
-
 def potatoMosaic(args):
     """entry point of ``snpmatch mosaic``"""
     given = lambda key, default: default if args.get(key) is None else args[key]      # noqa: E731
@@ -209,16 +200,7 @@ def potatoMosaic(args):
     samples, chrs, pos, gt = read_samples(args['inFile'], args.get('logDebug', False))
     log.info("loading genotype files!")
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    acc_ix = None
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        acc_ix = np.array(found, dtype=np.int64)
+    acc_ix, _ = _select.accessions_of(g, args)
     painted = Mosaic(samples, chrs, pos, gt, g, args['outFile'], switch_cost, mismatch, het_cost, min_seg, acc_ix)
     log.info("finished!")
     return painted.stats

@@ -30,7 +30,7 @@ import logging
 
 import numpy as np
 
-from . import csmatch, f1search, genomes, kinship, parsers, snp_genotype, snpmatch
+from . import _select, csmatch, f1search, genomes, parsers, snp_genotype, snpmatch
 
 log = logging.getLogger(__name__)
 
@@ -175,16 +175,7 @@ def potatoParentSearch(args):
     inputs = snpmatch.parse_inputs_once(args['inFile'], args.get('logDebug', False))
     log.info("loading genotype files!")
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    acc_ix = None
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        acc_ix = np.array(found, dtype=np.int64)
+    acc_ix, _ = _select.accessions_of(g, args)
     search = ParentSearch(inputs, g, given('genome', "athaliana_tair10"), int(given('binLen', 300000)), args['outFile'], int(given('top', TOP)),
                           int(given('min_sites', MIN_SITES)), int(given('min_win_sites', MIN_WIN_SITES)), acc_ix)
     log.info("finished!")

@@ -35,8 +35,7 @@ import logging
 
 import numpy as np
 
-from . import f1search, sitestats, snp_genotype
-from .ld import read_sites, rows_of_sites
+from . import _select, sitestats, snp_genotype
 
 log = logging.getLogger(__name__)
 
@@ -196,7 +195,7 @@ def project_samples(g, res, samples, chrs, pos, gt):
     matched[at[hit]] = True
     classes = np.full((len(samples), res["R"]), NO_CLASS, dtype=np.uint8)
     for s in range(len(samples)):
-        classes[s, at[hit]] = f1search.hard_classes(gt[:, s])[rec_rows[hit]]
+        classes[s, at[hit]] = _select.hard_classes(gt[:, s])[rec_rows[hit]]
     return project(classes, res["tab"], res["load"], res["eigenvalues"], res["R"], matched)
 
 
@@ -220,8 +219,7 @@ def write_projection(prefix, samples, coord, n_sites, names, vec, pop_of, pop_na
 
 def potatoPCA(args):
     """entry point of ``snpmatch pca``"""
-    if args.get('bed') and args.get('sitesFile'):
-        raise ValueError("give either --bed or --sites, not both")
+    _select.one_row_option(args)
     given = lambda key, default: default if args.get(key) is None else args[key]      # noqa: E731
     min_maf, max_missing, k = float(given('min_maf', 0.05)), float(given('max_missing', 0.1)), int(given('components', 10))
     if not 0.0 <= min_maf <= 0.5:
@@ -234,21 +232,15 @@ def potatoPCA(args):
         raise ValueError("a principal component analysis needs at least 2 accessions, got %d" % len(names))
     if not 1 <= k <= min(MAX_COMPONENTS, len(names)):
         raise ValueError("--components must be 1 .. %d (min(%d, accessions)), got %d" % (min(MAX_COMPONENTS, len(names)), MAX_COMPONENTS, k))
-    if args.get('sitesFile'):
-        rows = rows_of_sites(g, *read_sites(args['sitesFile']))
-    elif args.get('bed'):
-        rows = np.asarray(g.determine_snp_ix_given_bed(args['bed']), dtype=np.int64)
-    else:
-        rows = np.arange(len(g.g.positions), dtype=np.int64)
+    rows = _select.rows_of(g, args)
     log.info("pca: %d accessions, %d selected rows, %d components", len(names), len(rows), k)
     res = analyse(g, acc_ix, len(names), rows, min_maf, max_missing, k)
-    res["chr"], res["pos"] = sitestats.row_chromosomes(g, res["rows"]), np.asarray(g.g.positions)[res["rows"]].astype(np.int64)
+    res["chr"], res["pos"] = _select.row_chromosomes(g, res["rows"]), np.asarray(g.g.positions)[res["rows"]].astype(np.int64)
     settings = {"min_maf": min_maf, "max_missing": max_missing, "components": k, "populations": pop_names, "bed": args.get('bed'), "sites": args.get('sitesFile')}
     stats = write_outputs(args['outFile'], names, pop_of, res, settings, bool(args.get('keep_grm')))
     log.info("%d of %d rows used; PC1 %.3f, PC2 %.3f of the trace", res["R"], len(rows), stats["explained"][0], stats["explained"][1] if k > 1 else 0.0)
     if args.get('inFile'):
-        from . import mosaic
-        samples, chrs, pos, gt = mosaic.read_samples(args['inFile'], args.get('logDebug', False))
+        samples, chrs, pos, gt = _select.read_samples(args['inFile'], args.get('logDebug', False))
         coord, n_sites = project_samples(g, res, samples, chrs, pos, gt)
         write_projection(args['outFile'], samples, coord, n_sites, names, res["vec"], pop_of, pop_names)
         stats["projected"] = int(np.count_nonzero(n_sites > 0))

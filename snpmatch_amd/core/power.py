@@ -30,8 +30,7 @@ import logging
 
 import numpy as np
 
-from . import snp_genotype
-from .kinship import read_accession_list
+from . import _select, snp_genotype
 
 log = logging.getLogger(__name__)
 
@@ -170,22 +169,9 @@ class Power(object):
 
 def potatoPower(args):
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
-    acc_ix = None
-    if args.get('accFile'):
-        wanted = read_accession_list(args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        acc_ix = np.array(found, dtype=np.int64)
-    if args.get('bed') and args.get('sitesFile'):
-        raise ValueError("give either --bed or --sites, not both")
-    snp_ix = g.determine_snp_ix_given_bed(args['bed']) if args.get('bed') else None
-    if args.get('sitesFile'):           # a site list (chr, pos), e.g. the <prefix>.markers.tsv of the markers command
-        from .ld import read_sites, rows_of_sites
-        snp_ix = rows_of_sites(g, *read_sites(args['sitesFile']))
+    acc_ix, _ = _select.accessions_of(g, args)
+    # --sites: any site list (chr, pos), e.g. the <prefix>.markers.tsv of the markers command
+    snp_ix = _select.rows_of(g, args) if args.get('bed') or args.get('sitesFile') else None
     study = Power(g, parse_levels(args['levels']), args.get('err_rate', 0.001), args.get('trials', 3), args.get('seed', 1),
                   args.get('lr_thres', LR_THRES), acc_ix, snp_ix)
     log.info("power of %d accessions, levels %s, %d trials", len(study.names), study.levels, study.trials)

@@ -21,24 +21,10 @@ import logging
 
 import numpy as np
 
-from . import kinship, snp_genotype
+from . import _select, snp_genotype
+from ._select import read_populations, row_chromosomes  # noqa: F401  (the names tests and tools import)
 
 log = logging.getLogger(__name__)
-
-
-def read_populations(path):
-    """(accession, population) pairs of a two-column text file (blanks or tabs; # lines and empty lines are skipped)"""
-    pairs = []
-    with open(path) as fh:
-        for n, line in enumerate(fh, 1):
-            line = line.strip()
-            if not line or line.startswith("#"):
-                continue
-            fields = line.split()
-            if len(fields) < 2:
-                raise ValueError("%s line %d: expected an accession and a population, got %r" % (path, n, line))
-            pairs.append((fields[0], fields[1]))
-    return pairs
 
 
 def populations_of(g, args):
@@ -47,34 +33,16 @@ def populations_of(g, args):
         raise ValueError("give either -a / --accessions or --pops, not both")
     if args.get('popFile'):
         pairs = read_populations(args['popFile'])
-        if not pairs:
-            raise ValueError("the population file %s names no accession" % args['popFile'])
-        found = g.get_matching_accs_ix([a for a, _ in pairs])
-        missing = [a for (a, _), ix in zip(pairs, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
+        found = _select.indices_of(g, [a for a, _ in pairs], "population file", args['popFile'])
         pops = {}
         for (_, pop), ix in zip(pairs, found):
             pops.setdefault(pop, []).append(ix)
         names = list(pops)
         return names, {name: np.array(pops[name], dtype=np.int64) for name in names}, [len(pops[name]) for name in names]
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        return ["listed"], {"listed": np.array(found, dtype=np.int64)}, [len(found)]
+    acc_ix, _ = _select.accessions_of(g, args)
+    if acc_ix is not None:
+        return ["listed"], {"listed": acc_ix}, [len(acc_ix)]
     return ["all"], None, [len(g.accessions)]
-
-
-def row_chromosomes(g, rows):
-    """the chromosome name of each of the given DB rows"""
-    regions = np.asarray(g.g.chr_regions)
-    which = np.searchsorted(regions[:, 1], rows, side="right")
-    return np.asarray(g.chrs).astype("U")[which] if len(rows) else np.zeros(0, dtype="U1")
 
 
 def summary(names, n_listed, counts, maf):
@@ -132,8 +100,8 @@ def write_outputs(prefix, names, n_listed, chrs, pos, counts, min_informative=0,
 def potatoSiteStats(args):
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
     names, pops, n_listed = populations_of(g, args)
-    snp_ix = g.determine_snp_ix_given_bed(args['bed']) if args.get('bed') else None
-    rows = np.arange(len(g.g.positions)) if snp_ix is None else np.asarray(snp_ix)
+    rows = _select.rows_of(g, args)
+    snp_ix = rows if args.get('bed') else None
     log.info("site statistics of %d population(s) over %d rows", len(names), len(rows))
     counts = g.site_counts(pops, snp_ix)
     pos = np.asarray(g.g.positions)[rows].astype(np.int64)

@@ -405,7 +405,8 @@ class Genotype(object):
         homozygous and different.  None = all accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a
         dense range."""
         from .. import engine
-        return engine.kinship_counts(_resident_panel(self, "kinship needs"), filter_acc_ix, _rows_or_range(filter_snp_ix))
+        panel, rows = _scan_of(self, "kinship needs", filter_snp_ix)
+        return engine.kinship_counts(panel, filter_acc_ix, rows)
 
     def kinship_given_snps(self, filter_acc_ix=None, filter_snp_ix=None):
         """Kinship between all pairs of the listed accessions over the listed DB rows (core/snp_genotype.py:256-289): fp64 ndarray
@@ -423,7 +424,8 @@ class Genotype(object):
         listed row (0 ref, 1 alt, 2 het, 0xFF none).  None = all accessions / all rows; a row list that is a run ``r, r + 1, ...``
         is scanned as a dense range."""
         from .. import engine
-        return engine.f1_counts(_resident_panel(self, "the exhaustive F1 search needs"), sample_class, filter_acc_ix, _rows_or_range(filter_snp_ix))
+        panel, rows = _scan_of(self, "the exhaustive F1 search needs", filter_snp_ix)
+        return engine.f1_counts(panel, sample_class, filter_acc_ix, rows)
 
     def parent_counts(self, sample_class, win_off, min_win_sites=1, filter_acc_ix=None, filter_snp_ix=None):
         """(score, n_tot, w_first, w_het) int32 [n, n] of every pair of the listed accessions taken, window by window, as the parents
@@ -431,8 +433,8 @@ class Genotype(object):
         (``engine.parent_counts``).  ``sample_class``: uint8, one class per listed row (0 ref, 1 alt, 2 het, 0xFF none).  None = all
         accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        return engine.parent_counts(_resident_panel(self, "the parent search needs"), sample_class, win_off, min_win_sites, filter_acc_ix,
-                                    _rows_or_range(filter_snp_ix))
+        panel, rows = _scan_of(self, "the parent search needs", filter_snp_ix)
+        return engine.parent_counts(panel, sample_class, win_off, min_win_sites, filter_acc_ix, rows)
 
     def ibd_counts(self, win_off, min_win_sites=20, max_diff_ppm=1000, min_run=1, filter_acc_ix=None, filter_snp_ix=None, bits=True):
         """the dict of ``engine.ibd_counts`` -- w_used, w_shared, n_shared, d_shared, run_max, n_runs, w_in_runs int32 [n, n] and the
@@ -441,9 +443,8 @@ class Genotype(object):
         = all accessions / all rows; ``filter_snp_ix`` may be a ``range``; a row list that is a run ``r, r + 1, ...`` is scanned as
         a dense range."""
         from .. import engine
-        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
-        return engine.ibd_counts(_resident_panel(self, "the shared-segment scan needs"), win_off, min_win_sites, max_diff_ppm, min_run, filter_acc_ix,
-                                 rows, bits)
+        panel, rows = _scan_of(self, "the shared-segment scan needs", filter_snp_ix)
+        return engine.ibd_counts(panel, win_off, min_win_sites, max_diff_ppm, min_run, filter_acc_ix, rows, bits)
 
     def marker_select(self, depth=1, max_markers=None, coord=None, min_dist=0, eligible=None, filter_acc_ix=None, filter_snp_ix=None, first_gain=True):
         """the dict of ``engine.marker_select`` -- chosen, gain_at, n_chosen, remaining, stop_reason, need, first_gain -- of the greedy
@@ -451,9 +452,8 @@ class Genotype(object):
         are indices into the listed rows.  None = all accessions / all rows; ``filter_snp_ix`` may be a ``range``; a row list that is
         a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
-        return engine.marker_select(_resident_panel(self, "the marker selection needs"), depth, max_markers, coord, min_dist, eligible, filter_acc_ix,
-                                    rows, first_gain)
+        panel, rows = _scan_of(self, "the marker selection needs", filter_snp_ix)
+        return engine.marker_select(panel, depth, max_markers, coord, min_dist, eligible, filter_acc_ix, rows, first_gain)
 
     def gram(self, tab, filter_acc_ix=None, filter_snp_ix=None):
         """fp64 [n, n]: the Gram matrix ``sum_s t(s, i) t(s, j)`` of the listed accessions over the listed DB rows, made on the
@@ -461,23 +461,23 @@ class Genotype(object):
         missing call has value 0.  None = all accessions / all rows; ``filter_snp_ix`` may be a ``range``; a row list that is a run
         ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
-        return engine.gram(_resident_panel(self, "the principal component analysis needs"), tab, filter_acc_ix, rows)
+        panel, rows = _scan_of(self, "the principal component analysis needs", filter_snp_ix)
+        return engine.gram(panel, tab, filter_acc_ix, rows)
 
     def loadings(self, tab, vec, filter_acc_ix=None, filter_snp_ix=None):
         """fp64 [rows, k]: ``sum_i t(s, i) vec[i, c]`` over the listed accessions for every listed DB row, made on the resident
         panel (``engine.loadings``).  ``tab`` / ``filter_acc_ix`` / ``filter_snp_ix`` as for ``gram``; ``vec``: fp64 [n, k]."""
         from .. import engine
-        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
-        return engine.loadings(_resident_panel(self, "the principal component analysis needs"), tab, vec, filter_acc_ix, rows)
+        panel, rows = _scan_of(self, "the principal component analysis needs", filter_snp_ix)
+        return engine.loadings(panel, tab, vec, filter_acc_ix, rows)
 
     def admix(self, Q, F, n_iter=1, filter_acc_ix=None, filter_snp_ix=None, update_q=True, update_f=True):
         """(Q, F, loglik) after ``n_iter`` joint EM iterations of the admixture model on the listed accessions over the listed DB
         rows, made on the resident panel (``engine.admix``).  ``Q``: fp64 [n, K]; ``F``: fp64 [rows, K]; ``filter_acc_ix`` /
         ``filter_snp_ix`` as for ``gram``."""
         from .. import engine
-        rows = filter_snp_ix if isinstance(filter_snp_ix, range) else _rows_or_range(filter_snp_ix)
-        return engine.admix(_resident_panel(self, "the admixture model needs"), Q, F, n_iter, filter_acc_ix, rows, update_q, update_f)
+        panel, rows = _scan_of(self, "the admixture model needs", filter_snp_ix)
+        return engine.admix(panel, Q, F, n_iter, filter_acc_ix, rows, update_q, update_f)
 
     def sim_counts(self, grp_off, err_rate, seed, filter_acc_ix=None, filter_snp_ix=None):
         """(score, ninfo) int32 [n_grp, n, n] of the sample simulated from every listed accession (its calls at the listed DB rows,
@@ -485,7 +485,8 @@ class Genotype(object):
         cuts them, counted on the resident panel (``engine.sim_counts``).  Row a is the sample, column b the DB accession.  None = all
         accessions / all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        return engine.sim_counts(_resident_panel(self, "the power study needs"), grp_off, err_rate, seed, filter_acc_ix, _rows_or_range(filter_snp_ix))
+        panel, rows = _scan_of(self, "the power study needs", filter_snp_ix)
+        return engine.sim_counts(panel, grp_off, err_rate, seed, filter_acc_ix, rows)
 
     def mosaic(self, classes, chain_off, cost, switch_cost, filter_acc_ix=None, filter_snp_ix=None, want_col_cost=False):
         """(state, chain_cost, col_cost) of the samples painted as mosaics of the listed accessions over the listed DB rows, which
@@ -493,8 +494,8 @@ class Genotype(object):
         [n_samples, n_rows], one class per sample and listed row (0 ref, 1 alt, 2 het, 0xFF none).  None = all accessions / all
         rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        return engine.mosaic(_resident_panel(self, "the mosaic needs"), classes, chain_off, cost, switch_cost, filter_acc_ix, _rows_or_range(filter_snp_ix),
-                             want_col_cost)
+        panel, rows = _scan_of(self, "the mosaic needs", filter_snp_ix)
+        return engine.mosaic(panel, classes, chain_off, cost, switch_cost, filter_acc_ix, rows, want_col_cost)
 
     # ------------------------------------------------------------------ site statistics
     def site_counts(self, filter_acc_ix=None, filter_snps_ix=None):
@@ -503,7 +504,7 @@ class Genotype(object):
         G = 1), an index array (G = 1; a repeat counts as listed) or a dict name -> index array (G = len(dict), in the dict's
         order).  ``filter_snps_ix``: None = all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        panel, rows = _resident_panel(self, "site statistics need"), _rows_or_range(filter_snps_ix)
+        panel, rows = _scan_of(self, "site statistics need", filter_snps_ix)
         if isinstance(filter_acc_ix, dict):
             for name, ix in filter_acc_ix.items():
                 assert type(ix) is np.ndarray, "provide numpy arrays in a dictionary when giving subpopulations (%r)" % (name,)
@@ -549,7 +550,8 @@ class Genotype(object):
         and fp64 [n, band] (``ld_from_counts`` of them).  ``filter_acc_ix``: None = all accessions, else DISTINCT indices;
         ``filter_snps_ix``: None = all rows; a row list that is a run ``r, r + 1, ...`` is scanned as a dense range."""
         from .. import engine
-        return engine.ld_band(_resident_panel(self, "LD needs"), band, filter_acc_ix, _rows_or_range(filter_snps_ix), v_alt, v_het, min_n, counts, r2)
+        panel, rows = _scan_of(self, "LD needs", filter_snps_ix)
+        return engine.ld_band(panel, band, filter_acc_ix, rows, v_alt, v_het, min_n, counts, r2)
 
     def calculate_ld(self, snp_ix, accs_ix=None, v_alt=2, v_het=1, min_n=2):
         """The full symmetric r2 matrix, fp64 [n, n], of the listed DB rows among the listed accessions (core/snp_genotype.py:291-295
@@ -588,8 +590,8 @@ class Genotype(object):
         the accession list.  ``filter_snps_ix``: None = all rows, a ``range``, or a row list (a run ``r, r + 1, ...`` is scanned as
         a dense range)."""
         from .. import engine
-        rows = filter_snps_ix if isinstance(filter_snps_ix, range) else _rows_or_range(filter_snps_ix)
-        return engine.window_counts(_resident_panel(self, "window counts need"), win_off, filter_acc_ix, pairs, rows, acc_counts)
+        panel, rows = _scan_of(self, "window counts need", filter_snps_ix)
+        return engine.window_counts(panel, win_off, filter_acc_ix, pairs, rows, acc_counts)
 
     def genome_window_counts(self, genome_class, window_size, filter_acc_ix=None, pairs=None, acc_counts=True):
         """The same over the windows of a genome (``Genome.get_window_rows``): ``((chr_ix, start, end, first, last), acc, pair)``
@@ -695,11 +697,18 @@ def _resident_panel(g, who_needs):
     return panel
 
 
+def _scan_of(g, who_needs, snp_ix):
+    """(panel, rows) for a pass-through of ``Genotype`` to a scan of ``engine``: the resident panel, or the refusal that names
+    ``who_needs``, and the row filter as ``_rows_or_range`` hands it on.  A function, not a method: the pass-throughs ask of ``g``
+    nothing but ``panel()``."""
+    return _resident_panel(g, who_needs), _rows_or_range(snp_ix)
+
+
 def _rows_or_range(snp_ix):
-    """a row filter for the panel scans: None (all rows), a ``range`` where the list is a run ``r, r + 1, ...`` (scanned as a dense
-    range), else the list as int64"""
-    if snp_ix is None:
-        return None
+    """a row filter for the panel scans: None (all rows), a ``range`` as it is or where the list is a run ``r, r + 1, ...`` (scanned as
+    a dense range), else the list as int64"""
+    if snp_ix is None or isinstance(snp_ix, range):
+        return snp_ix
     rows = np.asarray(snp_ix, dtype=np.int64).reshape(-1)
     if len(rows) and rows[0] >= 0 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))):
         return range(int(rows[0]), int(rows[0]) + len(rows))

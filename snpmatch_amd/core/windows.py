@@ -25,7 +25,7 @@ import logging
 
 import numpy as np
 
-from . import genomes, kinship, snp_genotype
+from . import _select, genomes, snp_genotype
 
 log = logging.getLogger(__name__)
 
@@ -100,16 +100,7 @@ def potatoWindows(args):
         raise ValueError("--pairs_only needs --pairs")
     g = snp_genotype.Genotype(args['hdf5File'], args.get('hdf5accFile'))
     genome = genomes.Genome(given('genome', "athaliana_tair10"))
-    acc_ix, names = None, g.accessions.tolist()
-    if args.get('accFile'):
-        wanted = kinship.read_accession_list(args['accFile'])
-        if not wanted:
-            raise ValueError("the accession list %s names no accession" % args['accFile'])
-        found = g.get_matching_accs_ix(wanted)
-        missing = [w for w, ix in zip(wanted, found) if ix is None]
-        if missing:
-            raise ValueError("accessions not in the database: %s" % ", ".join(missing[:10]))
-        acc_ix, names = np.array(found, dtype=np.int64), wanted
+    acc_ix, names = _select.accessions_of(g, args)
     pair_names = pairs = None
     if args.get('pairsFile'):
         pair_names = read_pairs(args['pairsFile'])

@@ -750,6 +750,24 @@ def _row_selection(panel, rows):
     return row_idx, 0, len(row_idx)
 
 
+def _scan_args(panel, caller, cols, rows):
+    """the opening of the resident-panel scans: the panel check, ``cols`` (None, or indices as contiguous int32) with their number,
+    and ``rows`` as ``_row_selection`` gives them -- ``(ctx, cols, ncols, row_idx, row0, n_rows)``"""
+    _need_resident_panel(panel, caller)
+    if cols is None:
+        ncols = panel.n_acc
+    else:
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        ncols = len(cols)
+    return (panel.ctx, cols, ncols) + _row_selection(panel, rows)
+
+
+def _column_limit(ncols, limit, scan):
+    """the library's limit on the columns of one call (``SNPM_<scan>_MAX_ACCESSIONS``), refused before numpy is asked for the result arrays"""
+    if ncols > limit:
+        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_%s_MAX_ACCESSIONS)" % (ncols, limit, scan))
+
+
 KIN_MAX_ACCESSIONS = 11552     # SNPM_KIN_MAX_ACCESSIONS: columns of one ``kinship_counts`` call
 
 
@@ -761,16 +779,8 @@ def kinship_counts(panel, cols=None, rows=None):
     both are homozygous and equal, rows where both are homozygous and different.  The reference's kinship is
     ``(same - diff) / ninfo``.  Only a panel whose columns all live on one device can be asked: group (accession-sharded) and
     streamed panels are refused."""
-    _need_resident_panel(panel, "kinship_counts")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
-    if ncols > KIN_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_KIN_MAX_ACCESSIONS)" % (ncols, KIN_MAX_ACCESSIONS))
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "kinship_counts", cols, rows)
+    _column_limit(ncols, KIN_MAX_ACCESSIONS, "KIN")
     ninfo, same, diff = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(3))
     check(ctx.lib.snpm_panel_kinship_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(ninfo), ptr(same), ptr(diff)), ctx.h)
     return ninfo, same, diff
@@ -787,18 +797,10 @@ def f1_counts(panel, sample_class, cols=None, rows=None):
     where the F1 of the two columns (ref where both are 0, alt where both are 1, het where both are called and differ) has the
     sample's class, and rows where it is informative at all.  With one-hot weights ``hits`` is the reference's score of the pair
     (core/csmatch.py:115-125) and ``ninfo`` its numinfo.  Group (accession-sharded) and streamed panels are refused."""
-    _need_resident_panel(panel, "f1_counts")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "f1_counts", cols, rows)
     sample_class = np.ascontiguousarray(sample_class, dtype=np.uint8).reshape(-1)
     assert len(sample_class) == n_rows, "one sample class per selected row: %d classes, %d rows" % (len(sample_class), n_rows)
-    if ncols > F1X_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_F1X_MAX_ACCESSIONS)" % (ncols, F1X_MAX_ACCESSIONS))
+    _column_limit(ncols, F1X_MAX_ACCESSIONS, "F1X")
     hits, ninfo = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(2))
     check(ctx.lib.snpm_panel_f1_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(sample_class), ptr(hits), ptr(ninfo)), ctx.h)
     return hits, ninfo
@@ -815,20 +817,12 @@ def parent_counts(panel, sample_class, win_off, min_win_sites=1, cols=None, rows
     strictly the largest), or as the parent that fits better (a tie to the smaller position).  Returns ``(score, n_tot, w_first,
     w_het)``, int32 [n_cols, n_cols]: ``w_first[a, b]`` windows taken as column a, ``w_first[b, a]`` as column b, ``w_het`` as
     their F1.  Group (accession-sharded) and streamed panels are refused."""
-    _need_resident_panel(panel, "parent_counts")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "parent_counts", cols, rows)
     sample_class = np.ascontiguousarray(sample_class, dtype=np.uint8).reshape(-1)
     assert len(sample_class) == n_rows, "one sample class per selected row: %d classes, %d rows" % (len(sample_class), n_rows)
     win_off = np.ascontiguousarray(win_off, dtype=np.int64).reshape(-1)
     assert len(win_off) >= 1, "win_off holds n_win + 1 entries"
-    if ncols > F1X_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_F1X_MAX_ACCESSIONS)" % (ncols, F1X_MAX_ACCESSIONS))
+    _column_limit(ncols, F1X_MAX_ACCESSIONS, "F1X")
     score, n_tot, w_first, w_het = (np.empty((ncols, ncols), dtype=np.int32) for _ in range(4))
     check(ctx.lib.snpm_panel_parent_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(sample_class), ptr(win_off), len(win_off) - 1,
                                            int(min_win_sites), ptr(score), ptr(n_tot), ptr(w_first), ptr(w_het)), ctx.h)
@@ -850,18 +844,10 @@ def ibd_counts(panel, win_off, min_win_sites=20, max_diff_ppm=1000, min_run=1, c
     ``n_runs``, ``w_in_runs`` -- int32 [n_cols, n_cols], full and symmetric -- and ``used_bits`` / ``shared_bits``, uint32 [n_cols,
     n_cols, ceil(n_win / 32)] (window w is bit w % 32 of word w // 32; None with ``bits=False``).  Group (accession-sharded) and
     streamed panels are refused."""
-    _need_resident_panel(panel, "ibd_counts")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "ibd_counts", cols, rows)
     win_off = np.ascontiguousarray(win_off, dtype=np.int64).reshape(-1)
     assert len(win_off) >= 1, "win_off holds n_win + 1 entries"
-    if ncols > F1X_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_F1X_MAX_ACCESSIONS)" % (ncols, F1X_MAX_ACCESSIONS))
+    _column_limit(ncols, F1X_MAX_ACCESSIONS, "F1X")
     n_win = len(win_off) - 1
     out = {name: np.empty((ncols, ncols), dtype=np.int32) for name in IBD_COUNT_NAMES}
     out["used_bits"], out["shared_bits"] = ((np.empty((ncols, ncols, (n_win + 31) // 32), dtype=np.uint32) if bits else None) for _ in range(2))
@@ -888,17 +874,9 @@ def gram(panel, tab, cols=None, rows=None):
     in an order fixed by the arguments and ``SNPM_PCA_WS_MB``: the same call returns the same bits, and a table of small integers
     gives the exact integers.  A value of ``tab`` that is not finite is refused.  Group (accession-sharded) and streamed panels
     are refused."""
-    _need_resident_panel(panel, "gram")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "gram", cols, rows)
     tab = _class_table(tab, n_rows)
-    if ncols > PCA_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result array
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_PCA_MAX_ACCESSIONS)" % (ncols, PCA_MAX_ACCESSIONS))
+    _column_limit(ncols, PCA_MAX_ACCESSIONS, "PCA")
     out = np.empty((ncols, ncols), dtype=np.float64)
     check(ctx.lib.snpm_panel_gram(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(tab), ptr(out)), ctx.h)
     return out
@@ -908,14 +886,7 @@ def loadings(panel, tab, vec, cols=None, rows=None):
     """``load[s, c] = sum_i t(s, i) vec[i, c]`` over the listed accession columns for every selected row of a resident panel, in one
     device call (``snpm_panel_loadings``): with the eigenvectors of the Gram matrix as ``vec`` the raw SNP loadings ``Z V``.
     ``tab`` / ``cols`` / ``rows`` as for ``gram``; ``vec``: fp64 [n_cols, k], 1 <= k <= 32, finite.  Returns fp64 [n_rows, k]."""
-    _need_resident_panel(panel, "loadings")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "loadings", cols, rows)
     tab = _class_table(tab, n_rows)
     vec = np.ascontiguousarray(vec, dtype=np.float64)
     assert vec.ndim == 2 and vec.shape[0] == ncols, "vec is [n_cols, k]: got %r for %d columns" % (vec.shape, ncols)
@@ -941,14 +912,7 @@ def admix(panel, Q, F, n_iter=1, cols=None, rows=None, update_q=True, update_f=T
     the START of iteration t.  With ``update_q=False`` / ``update_f=False`` that component comes back with its bits; with both False
     the call only evaluates the likelihood.  fp64 throughout in an order fixed by the arguments: the same call returns the same bits.
     Group (accession-sharded) and streamed panels are refused."""
-    _need_resident_panel(panel, "admix")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "admix", cols, rows)
     Q, F = np.array(Q, dtype=np.float64, order="C"), np.array(F, dtype=np.float64, order="C")      # (copies: the call writes them)
     assert Q.ndim == 2 and Q.shape[0] == ncols, "Q is [n_cols, K]: got %r for %d columns" % (Q.shape, ncols)
     K = Q.shape[1]
@@ -979,16 +943,8 @@ def marker_select(panel, depth=1, max_markers=None, coord=None, min_dist=0, elig
     ``first_gain`` int32 [n_rows] (the pairs every row separates, whatever its eligibility; None with ``first_gain=False``; zeros from
     a call with fewer than two columns, no row or ``max_markers`` 0, which launches nothing).  Group (accession-sharded) and streamed
     panels are refused."""
-    _need_resident_panel(panel, "marker_select")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
-    if ncols > MK_MAX_ACCESSIONS:           # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_MK_MAX_ACCESSIONS)" % (ncols, MK_MAX_ACCESSIONS))
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "marker_select", cols, rows)
+    _column_limit(ncols, MK_MAX_ACCESSIONS, "MK")
     max_markers = MK_NO_LIMIT if max_markers is None else int(max_markers)
     if coord is not None:
         coord = np.ascontiguousarray(coord, dtype=np.int64).reshape(-1)
@@ -1030,21 +986,13 @@ def sim_counts(panel, grp_off, err_rate, seed, cols=None, rows=None):
     int32 [n_grp, n_cols, n_cols], NOT symmetric: ``ninfo[g, a, b]`` rows of group g where sample a has a call and column b's is not
     missing, ``score[g, a, b]`` rows where column b's code is sample a's class -- the reference's NumInfoSites / ScoreList of that
     sample against b.  Group (accession-sharded) and streamed panels are refused."""
-    _need_resident_panel(panel, "sim_counts")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "sim_counts", cols, rows)
     grp_off = np.ascontiguousarray(grp_off, dtype=np.int64).reshape(-1)
     assert len(grp_off) >= 1, "grp_off holds n_grp + 1 entries"
     n_grp = len(grp_off) - 1
     err_thr = sim_err_threshold(err_rate)
     seed = int(seed) % (1 << 64)
-    if ncols > SIM_MAX_ACCESSIONS:          # the library's limits, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_SIM_MAX_ACCESSIONS)" % (ncols, SIM_MAX_ACCESSIONS))
+    _column_limit(ncols, SIM_MAX_ACCESSIONS, "SIM")
     if not 1 <= n_grp <= SIM_MAX_GROUPS or n_grp * ncols * ncols >= 1 << 31:
         check(ctx.lib.snpm_panel_sim_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(grp_off), n_grp, err_thr, seed, None, None), ctx.h)
     score, ninfo = (np.empty((n_grp, ncols, ncols), dtype=np.int32) for _ in range(2))
@@ -1066,14 +1014,7 @@ def mosaic(panel, classes, chain_off, cost, switch_cost, cols=None, rows=None, w
     col_cost)``: int32 [n_samples, n_rows] positions in the column list, int32 [n_samples, n_chain], and int32 [n_samples, n_chain,
     n_cols] -- the cost of never switching -- or None without ``want_col_cost``.  Group (accession-sharded) and streamed panels are
     refused."""
-    _need_resident_panel(panel, "mosaic")
-    ctx = panel.ctx
-    if cols is None:
-        ncols = panel.n_acc
-    else:
-        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
-        ncols = len(cols)
-    row_idx, row0, n_rows = _row_selection(panel, rows)
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "mosaic", cols, rows)
     classes = np.ascontiguousarray(classes, dtype=np.uint8)
     if classes.ndim == 1:
         classes = classes.reshape(1, -1)
@@ -1089,8 +1030,7 @@ def mosaic(panel, classes, chain_off, cost, switch_cost, cols=None, rows=None, w
     switch_cost = int(switch_cost)
     if not -2 ** 31 <= switch_cost < 2 ** 31:
         raise AssertionError("switch_cost must be 1 .. 2^20")
-    if ncols > MOS_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_MOS_MAX_ACCESSIONS)" % (ncols, MOS_MAX_ACCESSIONS))
+    _column_limit(ncols, MOS_MAX_ACCESSIONS, "MOS")
     state = np.empty((n_samples, n_rows), dtype=np.int32)
     chain_cost = np.empty((n_samples, n_chain), dtype=np.int32)
     col_cost = np.empty((n_samples, n_chain, ncols), dtype=np.int32) if want_col_cost else None
@@ -1270,8 +1210,7 @@ def window_counts(panel, win_off, cols=None, pairs=None, rows=None, acc_counts=T
             raise TypeError("accession indices must be integers, got %s" % cols.dtype)
         cols = np.ascontiguousarray(cols, dtype=np.int32)
         ncols = len(cols)
-    if ncols > WIN_MAX_ACCESSIONS:          # the library's limit, before numpy is asked for the result arrays
-        raise AssertionError("too many accessions for one call: %d, at most %d (SNPM_WIN_MAX_ACCESSIONS)" % (ncols, WIN_MAX_ACCESSIONS))
+    _column_limit(ncols, WIN_MAX_ACCESSIONS, "WIN")
     pa = pb = None
     n_pairs = 0
     if pairs is not None:
