@@ -447,7 +447,8 @@ int snpm_profile_reset(snpm_ctx *ctx);
    "pca_gram" / "pca_fold" (the two kernels of snpm_panel_gram, one launch each per slab; its planes are a "win_planes" launch per
    slab), "pca_load" (the kernel of snpm_panel_loadings, one launch per slab), "adm_rows" / "adm_cols" / "adm_fold" (the three
    kernels of snpm_panel_admix: "adm_rows" and "adm_fold" one launch per iteration, "adm_cols" one per iteration with
-   SNPM_ADMIX_UPDATE_Q).
+   SNPM_ADMIX_UPDATE_Q), "mix_count" (the count kernel of snpm_panel_mix_counts, one launch per slab; its planes are a
+   "win_planes" launch per slab).
    Synchronises the stream. */
 int snpm_profile_read(snpm_ctx *ctx, const char *kernel, int64_t *launches, double *total_ms);
 
@@ -926,6 +927,33 @@ int snpm_panel_loadings(snpm_panel *panel, const int32_t *cols, int64_t ncols, c
 #define SNPM_ADMIX_UPDATE_Q 2u
 int snpm_panel_admix(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
                      int K, int n_iter, unsigned flags, double *Q, double *F, double *loglik /* [n_iter] */);
+
+/* ---------------------------------------------------------------- mixture */
+/* The read-count-weighted 2 x 2 table of EVERY ordered pair of listed accession columns against one sample's allele depths (the
+   FORMAT AD field of a VCF) over panel rows: what the likelihood of "a pool of accession a with a fraction alpha of accession b"
+   needs, for a contaminated or pooled sample -- on the RESIDENT panel (int8 or packed), as one call.  The package's own: the
+   reference has no such scan.  Host pointers in and out.
+     cols [ncols]     accession columns, any order, repeats allowed; NULL = all accessions (ncols must then be the panel's count)
+     row_idx [n_rows] panel rows, any order, repeats allowed; NULL = the dense range [row0, row0 + n_rows)
+     alt, ref [n_rows]   the sample's reads of the alt and of the ref allele at every selected row, 0 .. 255 each
+   On canonical DB codes (0, 1, 2, 3 = an int8 panel's "other" code, missing) a row counts for the pair (a, b) where BOTH columns
+   carry a homozygous call (0 or 1); a het, "other" or missing call on either side drops the row for that pair.
+     table [2][2][2][ncols][ncols]   table[w][ca][cb][a][b] = the sum, over the selected rows where column a has call ca and
+                                     column b has call cb, of the sample's alt (w = 0) or ref (w = 1) reads
+   Exact int32 sums; table[w][ca][cb][a][b] == table[w][cb][ca][b][a]; on the diagonal ca != cb gives 0 and ca == cb the sums of a
+   column on its own.  The row axis is processed in slabs whose bit-planes (4 bits per call) fit a workspace budget (512 MiB;
+   SNPM_MIX_WS_MB, read by snpm_init); two launches per slab, the sums accumulate on the device, so the result does not depend on
+   the budget.  The counts travel as 2, 4 or 8 bit slices each: the smallest that hold the largest count of the call.
+   Limits: ncols <= SNPM_MIX_MAX_ACCESSIONS (the tile pairs of the count kernel stay below 2^16), n_rows < 2^31, and
+   n_rows * the largest byte of alt / ref < 2^31 (the sums are int32).
+   Validated on the host before the device is touched (SNPM_ERR_BADARG with a message that names the rule): no negative size, the
+   limits, non-NULL table when ncols > 0, non-NULL alt and ref when n_rows > 0, the int32 rule -- these before the panel handle is
+   looked at, the message of a NULL panel is in snpm_last_error(NULL) -- then every column and row inside the panel, then ncols ==
+   the panel's accession count when cols is NULL.  ncols == 0 writes nothing; n_rows == 0 writes zeros without a launch.  Uploads
+   into the panel that are still in flight are waited for on the device. */
+#define SNPM_MIX_MAX_ACCESSIONS 11552
+int snpm_panel_mix_counts(snpm_panel *panel, const int32_t *cols, int64_t ncols, const int64_t *row_idx, int64_t row0, int64_t n_rows,
+                          const uint8_t *alt, const uint8_t *ref, int32_t *table /* [2][2][2][ncols][ncols] */);
 
 /* ---------------------------------------------------------------- sample input: VCF text (host only, no GPU) */
 /* Single pass over a (plain or gzip) VCF: what ParseInputs.read_vcf (core/parsers.py:178-213, scikit-allel in

@@ -62,6 +62,7 @@ SYMBOLS = [
     "snpm_panel_marker_select",
     "snpm_panel_gram", "snpm_panel_loadings",
     "snpm_panel_admix",
+    "snpm_panel_mix_counts",
 ]
 
 _lib = None
@@ -267,6 +268,7 @@ def load():
     lib.snpm_panel_gram.argtypes = [p, p, i64, p, i64, i64, p, p]
     lib.snpm_panel_loadings.argtypes = [p, p, i64, p, i64, i64, p, p, C.c_int, p]
     lib.snpm_panel_admix.argtypes = [p, p, i64, p, i64, i64, C.c_int, C.c_int, C.c_uint, p, p, p]
+    lib.snpm_panel_mix_counts.argtypes = [p, p, i64, p, i64, i64, p, p, p]
     lib.snpm_debug_stream_read.argtypes = [p, C.POINTER(i64)]
     lib.snpm_profile_enable.argtypes = [p, ci]
     lib.snpm_profile_reset.argtypes = [p]

@@ -9,6 +9,7 @@ Command line, one subcommand (or group of them) per line:
   * ``ld`` (the reference's ``calculate_ld`` does not run) computes r2 of neighbouring DB rows inside a band on the device and prunes the rows by it.
   * ``windows`` (not in the reference as a command) counts, per genome window, the heterozygosity of every accession and the mismatch of listed pairs of accessions on the device.
   * ``f1search`` (not in the reference) scores the in-silico F1 of EVERY pair of accessions against a sample on the device, where ``cross`` tries the ten best singles.
+  * ``mixture`` (not in the reference) reads the allele depths (FORMAT AD) of a sample and fits "accession a with a fraction alpha of accession b" to EVERY ordered pair of accessions from read sums counted on the device: a contaminated or pooled sample, which ``inbred`` and ``f1search`` do not see.
   * ``parentsearch`` (not in the reference) scores every pair of accessions per genome window as the parents of a recombinant sample (an F2, a backcross), where the sample is parent A in one window, the F1 in the next and parent B in a third.
   * ``simulate`` draws a test sample from the database as the reference does (host only, the same draws under one ``--seed``).
   * ``power`` (not in the reference) simulates a sample from EVERY accession and scores it against every accession on the device, for a whole ladder of marker counts: which accessions ``inbred`` identifies uniquely with n SNPs at a call error rate, and whom it confuses.
@@ -141,6 +142,12 @@ def snpmatch_f1search(args):
     from .core import f1search
     check_files(args, ('inFile', 'hdf5File'), ('accFile',))
     f1search.potatoF1Search(args)
+
+
+def snpmatch_mixture(args):
+    from .core import mixture
+    check_files(args, ('inFile', 'hdf5File'), ('accFile', 'sitesFile'))
+    mixture.potatoMixture(args)
 
 
 def snpmatch_parentsearch(args):
@@ -367,6 +374,23 @@ def get_options(description, version_message):
     verbose(f1s)
     f1s.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.f1search.scores.txt, <prefix>.f1search.npz and <prefix>.f1search.json")
     f1s.set_defaults(func=snpmatch_f1search)
+
+    # not in the reference: a contaminated or pooled sample -- reads of two accessions in unequal proportion -- from the allele balance of its reads
+    mx = sub.add_parser('mixture', help="a contaminated or pooled sample: the two accessions of the database and the minor fraction that explain the allele depths (FORMAT AD) of the sample best, EVERY ordered pair of accessions tried")
+    mx.add_argument("-i", "--input_file", dest="inFile", required=True, help="VCF file of the sample with FORMAT AD (allele depths)")
+    db_options(mx)
+    mx.add_argument("-a", "--accessions", dest="accFile", default=None, help="text file, one candidate accession name per line (default: all accessions)")
+    mx.add_argument("--bed", dest="bed", default=None, help="use the DB rows of a region only: Chr1,1,1000000 (default: all rows)")
+    mx.add_argument("--sites", dest="sitesFile", default=None, help="use the listed rows only: a file with the columns chr and pos (a <prefix>.pruned.tsv of ld, a <prefix>.markers.tsv of markers)")
+    mx.add_argument("--sample", dest="sample", default=None, help="sample column of the VCF: its name or its index (default 0)")
+    mx.add_argument("--err", dest="err", default=0.01, type=float, help="probability that a read shows the other allele (default 0.01)")
+    mx.add_argument("--grid", dest="grid", default=0.01, type=float, help="step of the minor fraction alpha on [0, 0.5]; must divide 0.5 (default 0.01)")
+    mx.add_argument("--max_depth", dest="max_depth", default=15, type=int, help="rows with more reads are dropped, 1 .. 255 (default 15)")
+    mx.add_argument("--min_reads", dest="min_reads", default=200, type=int, help="an ordered pair is ranked only with this many reads or more on the rows where both are homozygous (default 200)")
+    mx.add_argument("--top", dest="top", default=10, type=int, help="ordered pairs of the shortlist (default 10)")
+    verbose(mx)
+    mx.add_argument("-o", "--output", dest="outFile", required=True, help="Output prefix: writes <prefix>.mixture.json, <prefix>.mixture.npz and <prefix>.mixture.scores.txt")
+    mx.set_defaults(func=snpmatch_mixture)
 
     # not in the reference (its cross guesses the parents of an F2 from the single accessions that win clean windows): every pair per window
     par = sub.add_parser('parentsearch', help="parents of a recombinant sample (F2, backcross): EVERY pair of accessions of the database scored per genome window as parent A, parent B or their F1")

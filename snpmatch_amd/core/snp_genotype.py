@@ -427,6 +427,15 @@ class Genotype(object):
         panel, rows = _scan_of(self, "the exhaustive F1 search needs", filter_snp_ix)
         return engine.f1_counts(panel, sample_class, filter_acc_ix, rows)
 
+    def mix_counts(self, alt, ref, filter_acc_ix=None, filter_snp_ix=None):
+        """int32 [2, 2, 2, n, n]: for every ordered pair of the listed accessions the sample's alt and ref reads summed over the
+        listed DB rows by the pair's two homozygous calls, on the resident panel (``engine.mix_counts``).  ``alt`` / ``ref``: one
+        read count (0 .. 255) per listed row.  None = all accessions / all rows; a row list that is a run ``r, r + 1, ...`` is
+        scanned as a dense range."""
+        from .. import engine
+        panel, rows = _scan_of(self, "the mixture scan needs", filter_snp_ix)
+        return engine.mix_counts(panel, alt, ref, filter_acc_ix, rows)
+
     def parent_counts(self, sample_class, win_off, min_win_sites=1, filter_acc_ix=None, filter_snp_ix=None):
         """(score, n_tot, w_first, w_het) int32 [n, n] of every pair of the listed accessions taken, window by window, as the parents
         of a recombinant sample, over the listed DB rows grouped into windows by ``win_off``, counted on the resident panel

@@ -34,8 +34,8 @@ namespace {
 
 thread_local std::string g_init_error;
 
-enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_MK_P, PK_MK_G, PK_MK_K, PK_MK_U, PK_PCA_G, PK_PCA_F, PK_PCA_L, PK_ADM_R, PK_ADM_C, PK_ADM_F, PK_COUNT };
-const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs", "mk_planes", "mk_gain", "mk_pick", "mk_update", "pca_gram", "pca_fold", "pca_load", "adm_rows", "adm_cols", "adm_fold"};
+enum ProfKind { PK_FAST = 0, PK_STRICT, PK_REDUCE, PK_SCAN, PK_LIK, PK_SYNTH, PK_LUT, PK_GCROSS, PK_GHMM, PK_PAIRS_T, PK_PAIRS_C, PK_KIN_P, PK_KIN_C, PK_SITE, PK_LD_P, PK_LD_B, PK_WIN_P, PK_WIN_C, PK_F1X_C, PK_PAR_C, PK_SIM_N, PK_SIM_C, PK_MOS_F, PK_MOS_B, PK_IBD_C, PK_IBD_R, PK_MK_P, PK_MK_G, PK_MK_K, PK_MK_U, PK_PCA_G, PK_PCA_F, PK_PCA_L, PK_ADM_R, PK_ADM_C, PK_ADM_F, PK_MIX_C, PK_COUNT };
+const char *kProfNames[PK_COUNT] = {"fast", "strict", "reduce", "scan", "likelihood", "synth", "lut", "gcross", "ghmm", "pairs_t", "pairs_c", "kin_planes", "kin_count", "site_counts", "ld_planes", "ld_band", "win_planes", "win_count", "f1x_count", "par_count", "sim_noise", "sim_count", "mos_fwd", "mos_back", "ibd_count", "ibd_runs", "mk_planes", "mk_gain", "mk_pick", "mk_update", "pca_gram", "pca_fold", "pca_load", "adm_rows", "adm_cols", "adm_fold", "mix_count"};
 
 struct Buf {
     void *p = nullptr;
@@ -80,6 +80,8 @@ struct Buf {
     X(ws_pca_planes) X(ws_pca_tab) X(ws_pca_part) X(ws_pca_out) X(ws_pca_cols) X(ws_pca_vec) X(ws_pca_load)                       \
     /* snpm_panel_admix (snpm_api_adm.hpp): Q and Q' [2][ncols][KT]; F and F' [2][n_rows][KT]; partials [splits][ncols][KT]; the two buffers of the likelihood tree; loglik [n_iter]; column list */ \
     X(ws_adm_q) X(ws_adm_f) X(ws_adm_part) X(ws_adm_ll) X(ws_adm_out) X(ws_adm_cols)                                              \
+    /* snpm_panel_mix_counts (snpm_api_mix.hpp): bit-planes [4][cols_pad][W] of a slab; bit slices of the read counts of all rows; column list; the table [2][2][2][ncols][ncols] */ \
+    X(ws_mix_planes) X(ws_mix_masks) X(ws_mix_cols) X(ws_mix_out)                                                                 \
     /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
     /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
     X(ws_rows)                                                                                                                    \
@@ -136,6 +138,7 @@ struct snpm_ctx {
     size_t ibd_bits_bytes = size_t(2048) << 20; // SNPM_IBD_BITS_MB: the most the two device bitsets [ncols][ncols][wwords] of snpm_panel_ibd_counts may take
     size_t mk_ws_bytes = size_t(1024) << 20;    // SNPM_MK_WS_MB: the most the row planes of ALL selected rows of snpm_panel_marker_select may take (they stay resident for the whole loop: no slabs)
     size_t pca_ws_bytes = size_t(512) << 20;    // SNPM_PCA_WS_MB: bit-planes and table rows of one row slab of snpm_panel_gram; table rows and results of one row slab of snpm_panel_loadings
+    size_t mix_ws_bytes = size_t(512) << 20;    // SNPM_MIX_WS_MB: bit-planes of one row slab of snpm_panel_mix_counts
     // the automatic choice: calls per (sample, union row) slot from which the contraction is the cheaper pass -- measured on 64
     // samples x 200k SNPs x 1135 accessions: the contraction costs ~2.8 ns per union row, the per-sample pass 0.27 ns (int8) /
     // 0.16 ns (packed) per call
@@ -536,6 +539,7 @@ try {
     if (const char *s = getenv("SNPM_IBD_BITS_MB")) ctx->ibd_bits_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_MK_WS_MB")) ctx->mk_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_PCA_WS_MB")) ctx->pca_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    if (const char *s = getenv("SNPM_MIX_WS_MB")) ctx->mix_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;
@@ -701,6 +705,7 @@ int snpm_synchronize(snpm_ctx *ctx)
 
 #include "snpm_api_pca.hpp"
 #include "snpm_api_adm.hpp"
+#include "snpm_api_mix.hpp"
 // ---------------------------------------------------------------------------------------------- profiling
 int snpm_profile_enable(snpm_ctx *ctx, int on)
 {

@@ -47,6 +47,7 @@
 //   k_mk_rowplanes / k_mk_gain / k_mk_pick / k_mk_update  markers: a greedy minimal set of panel rows that separates every pair of accession columns -- bit-planes the other way round (one bit per accession, one word row per SNP, a ballot per word), per round the gain of every eligible row by AND + popcount against the bit matrix of unresolved pairs, the best row from one key per gain block, the need matrix decremented cell by cell and the bit matrix rebuilt by ballot.
 //   k_pca_gram / k_pca_fold / k_pca_load  pca: the class-table-weighted Gram matrix of the accession columns -- the planes of k_win_planes decoded to fp64 values in LDS, a 64 x 64 tile pair and a run of plane steps per block, a 4 x 4 register tile of fp64 FMAs per lane, partial sums with one owner each folded into the matrix in a fixed order -- and the loadings, a wave per panel row (the package's own: no counterpart in the reference).
 //   k_adm_rows / k_adm_cols / k_adm_fold  admixture: one joint EM iteration of the model of STRUCTURE / ADMIXTURE -- a wave per panel row for the new frequencies and the likelihood, a thread per accession column and run of rows for the new ancestries, partial sums with one owner each folded in a fixed order, the likelihood in a fixed tree; all fp64, IEEE division (the package's own: no counterpart in the reference).
+//   k_mix_count<2 / 4 / 8>  mixture: the read-count-weighted 2 x 2 table of EVERY ordered pair of accession columns against one sample's allele depths (FORMAT AD) -- planes P0 and P1 of k_win_planes, the tiling of k_f1x_count, the alt and ref counts as 2 / 4 / 8 bit slices each; eight int32 sums per pair by AND + popcount + shift, 64 rows per word (the package's own: no counterpart in the reference).
 //   k_f1_*     in-silico F1 scores in numpy's summation order (core/csmatch.py:115-125).
 //   k_build_lut, k_repitch_canon / k_pack_rows / k_unpack_rows (upload / download), k_pack_transpose[_packed]
 //   (accession-major copies), k_synth* / k_synth_sample (benchmark data), k_check_rows, k_expand_codes, k_seg_pack,
@@ -78,5 +79,6 @@
 #include "snpm_k_mk.hpp"          // k_mk_rowplanes, k_mk_gain, k_mk_pick, k_mk_update (markers: a greedy minimal set of rows that separates every pair of accessions)
 #include "snpm_k_pca.hpp"         // k_pca_gram, k_pca_fold, k_pca_load (pca: the weighted Gram matrix of the accession columns and the row-streaming product for the loadings)
 #include "snpm_k_adm.hpp"         // k_adm_rows, k_adm_cols, k_adm_fold (admixture: one joint EM iteration of the ancestry model over the accession columns)
+#include "snpm_k_mix.hpp"         // k_mix_count (mixture: alt / ref read sums per pair of homozygous calls of every ordered pair of accessions)
 #include "snpm_k_io.hpp"          // k_pack_rows, k_repitch_canon, k_unpack_rows, k_synth*, k_calib_read
 #include "snpm_kernels_single.hpp"   // k_strict_single (panels of one accession: numpy's pairwise order)

@@ -806,6 +806,30 @@ def f1_counts(panel, sample_class, cols=None, rows=None):
     return hits, ninfo
 
 
+MIX_MAX_ACCESSIONS = 11552     # SNPM_MIX_MAX_ACCESSIONS: columns of one ``mix_counts`` call
+
+
+def mix_counts(panel, alt, ref, cols=None, rows=None):
+    """The read-count-weighted 2 x 2 table of every ordered pair of accession columns of a resident panel against one sample's
+    allele depths, in one device call (``snpm_panel_mix_counts``).  ``alt`` / ``ref``: the sample's reads of the alt and of the ref
+    allele at every selected row, 0 .. 255 each; ``cols`` / ``rows`` as for ``kinship_counts``.  Returns int32 [2, 2, 2, n_cols,
+    n_cols]: ``table[w, ca, cb, a, b]`` is the sum, over the rows where column a has the homozygous call ca and column b the
+    homozygous call cb, of the alt (w = 0) or ref (w = 1) reads; a het, "other" or missing call on either side drops the row for that
+    pair.  ``table[w, ca, cb, a, b] == table[w, cb, ca, b, a]``; the diagonal holds the sums of every column on its own.  Group
+    (accession-sharded) and streamed panels are refused."""
+    ctx, cols, ncols, row_idx, row0, n_rows = _scan_args(panel, "mix_counts", cols, rows)
+    counts = []
+    for name, v in (("alt", alt), ("ref", ref)):
+        v = np.asarray(v).reshape(-1)
+        assert len(v) == n_rows, "one %s count per selected row: %d counts, %d rows" % (name, len(v), n_rows)
+        assert v.dtype.kind in "iu" and (len(v) == 0 or (0 <= v.min() and v.max() <= 255)), "%s counts are integers 0 .. 255" % name
+        counts.append(np.ascontiguousarray(v, dtype=np.uint8))
+    _column_limit(ncols, MIX_MAX_ACCESSIONS, "MIX")
+    table = np.empty((2, 2, 2, ncols, ncols), dtype=np.int32)
+    check(ctx.lib.snpm_panel_mix_counts(panel.h, ptr(cols), ncols, ptr(row_idx), row0, n_rows, ptr(counts[0]), ptr(counts[1]), ptr(table)), ctx.h)
+    return table
+
+
 def parent_counts(panel, sample_class, win_off, min_win_sites=1, cols=None, rows=None):
     """Every pair of accession columns of a resident panel scored, window by window, as the two parents of a recombinant sample (an
     F2, a backcross, a RIL with residual heterozygosity) against the sample's hard calls, in one device call
