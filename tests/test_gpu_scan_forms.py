@@ -1,11 +1,15 @@
-"""The forms of ``rows`` and ``cols`` of the ten resident-panel scans on the device: a scan asked for every row as ``None``, as
+"""The forms of ``rows`` and ``cols`` of the eleven resident-panel scans that take a free column list, on the device (``mix_counts``
+is the eleventh; the calls are those of the table in tests/scan_cases.py): a scan asked for every row as ``None``, as
 ``slice(0, n)`` and as ``range(0, n)``, and for every column as ``None`` and as ``arange(n_acc)``, gives the same bits; the scans
 that count integers give the same counts for the row LIST ``arange(n)`` too.  The fp64 scans (``gram``, ``loadings``, ``admix``) are
 compared among the dense forms only: their summation order is fixed by the arguments, and a row list is a different argument.  One
 int8 and one packed panel of 70 rows by 67 accessions: 67 crosses the 64-column tile, 70 a 64-row step.  No tolerance anywhere."""
+import types
+
 import numpy as np
 import pytest
 
+import scan_cases
 from snpmatch_amd import engine
 from snpmatch_amd.core import admixture
 
@@ -20,19 +24,13 @@ VEC = _rng.normal(size=(N_ACC, 3))
 Q0, F0 = admixture.random_start(7, N_ACC, N_ROWS, 2)
 COST = np.array([[0, 2, 1, 2], [2, 0, 1, 2], [1, 1, 0, 2]], dtype=np.uint8)
 
-# scan -> (the call on (panel, cols, rows), whether it counts integers)
-SCANS = {
-    "kinship_counts": (lambda p, c, r: engine.kinship_counts(p, c, r), True),
-    "f1_counts": (lambda p, c, r: engine.f1_counts(p, CLASSES[0], c, r), True),
-    "parent_counts": (lambda p, c, r: engine.parent_counts(p, CLASSES[0], WIN_OFF, 1, c, r), True),
-    "ibd_counts": (lambda p, c, r: engine.ibd_counts(p, WIN_OFF, 2, 100000, 1, c, r), True),
-    "gram": (lambda p, c, r: engine.gram(p, TAB, c, r), False),
-    "loadings": (lambda p, c, r: engine.loadings(p, TAB, VEC, c, r), False),
-    "admix": (lambda p, c, r: engine.admix(p, Q0, F0, 2, c, r), False),
-    "marker_select": (lambda p, c, r: engine.marker_select(p, 1, None, None, 0, None, c, r), True),
-    "sim_counts": (lambda p, c, r: engine.sim_counts(p, [0, 30, N_ROWS], 0.01, 5, c, r), True),
-    "mosaic": (lambda p, c, r: engine.mosaic(p, CLASSES, [0, 40, N_ROWS], COST, 5, c, r, want_col_cost=True), True),
-}
+ALT, REF = (_rng.integers(0, 256, size=N_ROWS).astype(np.uint8) for _ in range(2))
+# the arguments of tests/scan_cases.py, whose table holds the calls
+ARGS = types.SimpleNamespace(cls=CLASSES, win_off=WIN_OFF, par_min_sites=1, ibd=(2, 100000, 1), tab=TAB, vec=VEC, Q=Q0, F=F0, n_iter=2, mk_depth=1, mk_max=None,
+                             grp_off=[0, 30, N_ROWS], err_rate=0.01, seed=5, chain_off=[0, 40, N_ROWS], cost=COST, switch=5, alt=ALT, ref=REF)
+# the scans of the table with ``cols`` any list and ``rows``; ``site_counts`` (groups), ``ld_band`` (distinct columns) and ``window_counts`` (pairs)
+# have their forms in their own files
+SCANS = ["kinship_counts", "f1_counts", "parent_counts", "ibd_counts", "mix_counts", "gram", "loadings", "admix", "marker_select", "sim_counts", "mosaic"]
 
 
 @pytest.fixture(scope="module", params=["int8", "packed"])
@@ -55,7 +53,8 @@ def _same_bits(a, b):
 
 @pytest.mark.parametrize("scan", sorted(SCANS))
 def test_every_form_of_all_rows_and_all_columns_gives_the_same_bits(panel, scan):
-    call, counts_integers = SCANS[scan]
+    entry = scan_cases.SCANS[scan]
+    call, counts_integers = (lambda p, c, r: entry.call(p, ARGS, c, r)), entry.counts_integers
     first = call(panel, None, None)
     assert any(np.asarray(a).any() for a in (first.values() if isinstance(first, dict) else first if isinstance(first, tuple) else [first])
                if isinstance(a, np.ndarray)), "a result of zeros compares nothing"
