@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "snpm_kernels.hpp"
+#include "snpm_scratch.hpp"
 
 using namespace snpm;
 
@@ -56,35 +57,11 @@ struct Buf {
     X(ws_gh_codes) X(ws_gh_depth) X(ws_gh_bp) X(ws_gh_state) X(ws_gh_pair) X(ws_gh_off) X(ws_gh_tab) X(ws_gh_omega)               \
     /* snpm_pair_counts (snpm_api_pairs.hpp): ids [n, pitch]; sample-major planes [pitch, n_pad]; chunk table; common | match */  \
     X(ws_pr_ids) X(ws_pr_planes) X(ws_pr_chunks) X(ws_pr_out)                                                                     \
-    /* snpm_panel_kinship_counts (snpm_api_kin.hpp): bit-planes [3][cols_pad][W] of a slab; column list; ninfo | same | diff */ \
-    X(ws_kin_planes) X(ws_kin_cols) X(ws_kin_out)                                                                                 \
-    /* snpm_panel_site_counts (snpm_api_site.hpp): membership bitmasks [groups][words]; counts [groups][slab rows][4] */ \
-    X(ws_site_member) X(ws_site_out)                                                                                              \
-    /* snpm_panel_ld_band (snpm_api_ld.hpp): membership words; planes [slab rows + band][3][words]; counts and r2 of a slab */   \
-    X(ws_ld_member) X(ws_ld_planes) X(ws_ld_counts) X(ws_ld_r2)                                                                   \
-    /* snpm_panel_window_counts (snpm_api_win.hpp): bit-planes [4][cols_pad][W] and cells of a slab; column list; pa | pb; win_off */ \
-    X(ws_win_planes) X(ws_win_cells) X(ws_win_cols) X(ws_win_pairs) X(ws_win_off)                                                 \
-    /* snpm_panel_f1_counts (snpm_api_f1x.hpp): bit-planes [4][cols_pad][W] of a slab; sample masks of all rows; column list; hits | ninfo */ \
-    X(ws_f1x_planes) X(ws_f1x_masks) X(ws_f1x_cols) X(ws_f1x_out)                                                                 \
-    /* snpm_panel_parent_counts (snpm_api_par.hpp): bit-planes [4][cols_pad][W] of a slab; group table; step offsets; segments; column list; score | n_tot | w_first | w_het */ \
-    X(ws_par_planes) X(ws_par_groups) X(ws_par_steps) X(ws_par_segs) X(ws_par_cols) X(ws_par_out)                                 \
-    /* snpm_panel_sim_counts (snpm_api_sim.hpp): bit-planes [4 + 3][cols_pad][W] of a slab; grp_off; column list; score | ninfo */ \
-    X(ws_sim_planes) X(ws_sim_grp) X(ws_sim_cols) X(ws_sim_out)                                                                   \
-    /* snpm_panel_mosaic (snpm_api_mos.hpp): bit-planes [4][cols_pad][W] of a slab of whole chains; sw words, j | state and class words of a group of samples; chain table; column list; chain_cost | col_cost */ \
-    X(ws_mos_planes) X(ws_mos_sw) X(ws_mos_j) X(ws_mos_cls) X(ws_mos_chains) X(ws_mos_cols) X(ws_mos_out)                         \
-    /* snpm_panel_ibd_counts (snpm_api_ibd.hpp): bit-planes [4][cols_pad][W] of a slab; group table; step offsets; segments; column list; the seven matrices; used | shared bitsets */ \
-    X(ws_ibd_planes) X(ws_ibd_groups) X(ws_ibd_steps) X(ws_ibd_segs) X(ws_ibd_cols) X(ws_ibd_out) X(ws_ibd_bits)                  \
-    /* snpm_panel_marker_select (snpm_api_mk.hpp): row planes [n_rows][2][Wc]; Ut [Wc][cols_pad]; need; gains; block keys; eligibility; coordinates; chosen | gain_at; MkState; column list */ \
-    X(ws_mk_planes) X(ws_mk_ut) X(ws_mk_need) X(ws_mk_gain) X(ws_mk_best) X(ws_mk_elig) X(ws_mk_coord) X(ws_mk_chosen) X(ws_mk_state) X(ws_mk_cols) \
-    /* snpm_panel_gram / snpm_panel_loadings (snpm_api_pca.hpp): bit-planes [4][cols_pad][W] and table rows of a slab; partials [splits][tile pairs][64][64]; the matrix; column list; vec; loadings of a slab */ \
-    X(ws_pca_planes) X(ws_pca_tab) X(ws_pca_part) X(ws_pca_out) X(ws_pca_cols) X(ws_pca_vec) X(ws_pca_load)                       \
-    /* snpm_panel_admix (snpm_api_adm.hpp): Q and Q' [2][ncols][KT]; F and F' [2][n_rows][KT]; partials [splits][ncols][KT]; the two buffers of the likelihood tree; loglik [n_iter]; column list */ \
-    X(ws_adm_q) X(ws_adm_f) X(ws_adm_part) X(ws_adm_ll) X(ws_adm_out) X(ws_adm_cols)                                              \
-    /* snpm_panel_mix_counts (snpm_api_mix.hpp): bit-planes [4][cols_pad][W] of a slab; bit slices of the read counts of all rows; column list; the table [2][2][2][ncols][ncols] */ \
-    X(ws_mix_planes) X(ws_mix_masks) X(ws_mix_cols) X(ws_mix_out)                                                                 \
-    /* the row list of ONE slab of a panel scan (snpm_api_rows.hpp).  One buffer for all: a context has one stream, and         */ \
-    /* each call synchronises it before it returns, so no call's rows are in flight when the next call writes its own.          */ \
-    X(ws_rows)                                                                                                                    \
+    /* the device scratch of ONE resident-panel scan (kinship ... mixture: snpm_api_{kin,site,ld,win,f1x,par,sim,mos,ibd,mk,pca,adm,mix}.hpp), */ \
+    /* its parts laid out per call by Scratch (snpm_scratch.hpp, scratch_commit).  One buffer for all: a context has one stream, */ \
+    /* each scan sizes all of its scratch before it queues anything and synchronises the stream before it returns, so no call's  */ \
+    /* scratch is in flight when the next call writes its own; a call initialises every part it reads.    */ \
+    X(ws_scan)                                                                                                                    \
     X(ws_once) X(ws_once_table)     /* snpm_genotype_once: its packed results (unfused form); the weight table of its coded form */ \
     X(ws_once_state)                /* {ticket, bad-input bits} of k_once_prep / k_once_finish: zero between calls */             \
     /* segmented / batched scoring */                                                                                             \
@@ -525,21 +502,16 @@ try {
     if (const char *s = getenv("SNPM_BATCH_SHARED")) ctx->batch_shared = atoi(s) < 0 ? -1 : (atoi(s) ? 1 : 0);
     if (const char *s = getenv("SNPM_SHARED_DIGITS")) ctx->shared_digits = atoi(s) <= 0 ? 0 : std::min(7, std::max(3, atoi(s)));
     if (const char *s = getenv("SNPM_SHARED_MIN_DENSITY")) ctx->shared_min_density = atof(s);
-    if (const char *s = getenv("SNPM_SHARED_WS_MB")) ctx->shared_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
     if (const char *s = getenv("SNPM_SHARED_TILES")) ctx->shared_force_tiles = std::max(0, atoi(s));
-    if (const char *s = getenv("SNPM_KIN_WS_MB")) ctx->kin_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_SITE_WS_MB")) ctx->site_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_LD_WS_MB")) ctx->ld_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_WIN_WS_MB")) ctx->win_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_F1X_WS_MB")) ctx->f1x_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_PAR_WS_MB")) ctx->par_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_SIM_WS_MB")) ctx->sim_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_MOS_WS_MB")) ctx->mos_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_IBD_WS_MB")) ctx->ibd_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_IBD_BITS_MB")) ctx->ibd_bits_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_MK_WS_MB")) ctx->mk_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_PCA_WS_MB")) ctx->pca_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
-    if (const char *s = getenv("SNPM_MIX_WS_MB")) ctx->mix_ws_bytes = (size_t)std::max(1, atoi(s)) << 20;
+    // the budgets in MiB (at least 1), read when the context is created
+    static const struct { const char *name; size_t snpm_ctx::*bytes; } kMegabyteKnobs[] = {
+        {"SNPM_SHARED_WS_MB", &snpm_ctx::shared_ws_bytes}, {"SNPM_KIN_WS_MB", &snpm_ctx::kin_ws_bytes}, {"SNPM_SITE_WS_MB", &snpm_ctx::site_ws_bytes},
+        {"SNPM_LD_WS_MB", &snpm_ctx::ld_ws_bytes}, {"SNPM_WIN_WS_MB", &snpm_ctx::win_ws_bytes}, {"SNPM_F1X_WS_MB", &snpm_ctx::f1x_ws_bytes},
+        {"SNPM_PAR_WS_MB", &snpm_ctx::par_ws_bytes}, {"SNPM_SIM_WS_MB", &snpm_ctx::sim_ws_bytes}, {"SNPM_MOS_WS_MB", &snpm_ctx::mos_ws_bytes},
+        {"SNPM_IBD_WS_MB", &snpm_ctx::ibd_ws_bytes}, {"SNPM_IBD_BITS_MB", &snpm_ctx::ibd_bits_bytes}, {"SNPM_MK_WS_MB", &snpm_ctx::mk_ws_bytes},
+        {"SNPM_PCA_WS_MB", &snpm_ctx::pca_ws_bytes}, {"SNPM_MIX_WS_MB", &snpm_ctx::mix_ws_bytes}};
+    for (const auto &k : kMegabyteKnobs)
+        if (const char *s = getenv(k.name)) ctx->*k.bytes = (size_t)std::max(1, atoi(s)) << 20;
     ctx->stage_threads = default_stage_threads();
     if (const char *s = getenv("SNPM_STAGE_THREADS")) ctx->stage_threads = std::max(1, atoi(s));
     if (const char *s = getenv("SNPM_STAGE_MB")) ctx->ld_want = (size_t)std::max(1, atoi(s)) << 20;

@@ -8,7 +8,7 @@
 //
 // No slabs and no workspace knob: the panel is resident, the row list (8 bytes per row) travels once, Q and F are copied in once
 // into rows of adm_pitch(K) doubles, double-buffered -- an iteration reads one pair and writes the other, a component that is not
-// updated is not swapped -- and are copied out once; ensure reports what does not fit.  Per iteration k_adm_rows (F', the likelihood
+// updated is not swapped -- and are copied out once; scratch_commit reports what does not fit.  Per iteration k_adm_rows (F', the likelihood
 // per block of rows), with SNPM_ADMIX_UPDATE_Q k_adm_cols (the partials of its splits), and k_adm_fold (Q', the likelihood).
 extern "C++" {                              // (a template cannot have C linkage)
 namespace {
@@ -84,18 +84,20 @@ try {
     const int kt = adm_pitch(K);
     const size_t q_doubles = (size_t)ncols * (size_t)kt, f_doubles = (size_t)n_rows * (size_t)kt;
     const int64_t n_ll = adm_ll_blocks(n_rows), splits = adm_splits(n_rows, ncols);
-    if ((rc = ensure(ctx, ctx->ws_adm_q, 2 * q_doubles * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_adm_f, 2 * f_doubles * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_adm_part, (size_t)splits * q_doubles * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_adm_ll, (size_t)(n_ll + (n_ll + ADM_TREE_RADIX - 1) / ADM_TREE_RADIX) * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_adm_out, (size_t)n_iter * sizeof(double)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_adm_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, n_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_adm_cols.p : nullptr;
-    double *d_q[2] = {(double *)ctx->ws_adm_q.p, (double *)ctx->ws_adm_q.p + q_doubles};
-    double *d_f[2] = {(double *)ctx->ws_adm_f.p, (double *)ctx->ws_adm_f.p + f_doubles};
-    double *d_part = (double *)ctx->ws_adm_part.p, *d_ll = (double *)ctx->ws_adm_ll.p, *d_out = (double *)ctx->ws_adm_out.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_adm_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;     // Q and Q' [2][ncols][KT]; F and F' [2][n_rows][KT]; partials [splits][ncols][KT]; the two buffers of the likelihood tree; loglik [n_iter]; column list; row list
+    double *d_qq, *d_ff, *d_part, *d_ll, *d_out;
+    int32_t *d_cols = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_qq, 2 * q_doubles);
+    sc.want(d_ff, 2 * f_doubles);
+    sc.want(d_part, (size_t)splits * q_doubles);
+    sc.want(d_ll, (size_t)(n_ll + (n_ll + ADM_TREE_RADIX - 1) / ADM_TREE_RADIX));
+    sc.want(d_out, (size_t)n_iter);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)n_rows);
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    double *d_q[2] = {d_qq, d_qq + q_doubles}, *d_f[2] = {d_ff, d_ff + f_doubles};
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     // rows of kt doubles, the entries at and beyond K zero, in both copies: k_adm_rows never writes them
     std::vector<double> hq(q_doubles, 0.0), hf(f_doubles, 0.0);
     for (int64_t i = 0; i < ncols; ++i) memcpy(&hq[(size_t)i * kt], Q + i * K, (size_t)K * sizeof(double));
@@ -105,7 +107,7 @@ try {
     HIPCHK(ctx, hipMemsetAsync(d_q[1], 0, q_doubles * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_f[1], 0, f_doubles * sizeof(double), ctx->stream));
     int at_q = 0, at_f = 0;
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, n_rows, [&](const int64_t *d_rows, int64_t first, int64_t, int64_t) {      // (one slab: all rows)
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, n_rows, [&](const int64_t *d_rows, int64_t first, int64_t, int64_t) {      // (one slab: all rows)
         for (int t = 0; t < n_iter; ++t) {
             switch (kt) {
             case 4: adm_launch<4>(ctx, p, d_rows, first, n_rows, d_cols, ncols, K, flags, d_q[at_q], d_q[at_q ^ 1], d_f[at_f], d_f[at_f ^ 1], d_part, d_ll, d_out + t); break;

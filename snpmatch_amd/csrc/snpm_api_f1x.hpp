@@ -42,20 +42,22 @@ try {
     const int64_t all_steps = (n_rows + F1X_STEP_ROWS - 1) / F1X_STEP_ROWS;
     std::vector<unsigned long long> masks((size_t)all_steps * F1X_MASK_WORDS);      // (lives until the stream is synchronised)
     f1x_fill_masks(sample_class, n_rows, masks.data());
-    if ((rc = ensure(ctx, ctx->ws_f1x_planes, (size_t)slab_steps * (size_t)f1x_step_bytes(cols_pad)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_f1x_masks, masks.size() * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_f1x_out, 2 * cells * sizeof(int32_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_f1x_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_f1x_cols.p : nullptr;
-    int32_t *d_hits = (int32_t *)ctx->ws_f1x_out.p, *d_ninfo = d_hits + cells;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_f1x_planes.p;
-    const unsigned long long *d_masks = (const unsigned long long *)ctx->ws_f1x_masks.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_f1x_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_f1x_masks.p, masks.data(), masks.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // bit-planes [4][cols_pad][W] of a slab; sample masks of all rows; hits | ninfo; column list; row list
+    unsigned long long *d_planes, *d_masks;
+    int32_t *d_hits, *d_cols = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_planes, (size_t)slab_steps * (size_t)f1x_step_bytes(cols_pad) / 8);
+    sc.want(d_masks, masks.size());
+    sc.want(d_hits, 2 * cells);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    int32_t *d_ninfo = d_hits + cells;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_masks, masks.data(), masks.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_hits, 0, 2 * cells * sizeof(int32_t), ctx->stream));
     // the results accumulate on the device across slabs
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         const int64_t W = (n_valid + F1X_STEP_ROWS - 1) / F1X_STEP_ROWS * F1X_STEP_WORDS;    // words per plane row of this slab
         {
             ProfScope ps(ctx, PK_WIN_P);

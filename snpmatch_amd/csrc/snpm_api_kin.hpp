@@ -35,17 +35,20 @@ int snpm_panel_kinship_counts(snpm_panel *panel, const int32_t *cols, int64_t nc
     const int n_tiles = (int)((ncols + KN_TILE - 1) / KN_TILE);
     // slabs of the row axis: whole LDS steps of planes inside the workspace budget (kin_slab_steps of snpm_k_kin.hpp)
     const int64_t slab_steps = kin_slab_steps(ctx->kin_ws_bytes, cols_pad, n_rows), slab_rows = slab_steps * KN_STEP_ROWS;
-    if ((rc = ensure(ctx, ctx->ws_kin_planes, (size_t)slab_steps * (size_t)kin_step_bytes(cols_pad)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_kin_out, 3 * cells * sizeof(int32_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_kin_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_kin_cols.p : nullptr;
-    int32_t *d_ninfo = (int32_t *)ctx->ws_kin_out.p, *d_same = d_ninfo + cells, *d_diff = d_same + cells;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_kin_planes.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_kin_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                       // bit-planes [3][cols_pad][W] of a slab; ninfo | same | diff; column list; row list
+    unsigned long long *d_planes;
+    int32_t *d_ninfo, *d_cols = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_planes, (size_t)slab_steps * (size_t)kin_step_bytes(cols_pad) / 8);
+    sc.want(d_ninfo, 3 * cells);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    int32_t *d_same = d_ninfo + cells, *d_diff = d_same + cells;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_ninfo, 0, 3 * cells * sizeof(int32_t), ctx->stream));
     // the results accumulate on the device across slabs
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t, int64_t n_valid) {
         const int64_t W = (n_valid + KN_STEP_ROWS - 1) / KN_STEP_ROWS * KN_STEP_WORDS;      // words per plane row of this slab
         {
             ProfScope ps(ctx, PK_KIN_P);

@@ -41,17 +41,20 @@ try {
     int rc = wait_upload(p);
     if (rc) return rc;
     const int64_t slab_rows = ld_slab_rows(ctx->ld_ws_bytes, words, band, n_rows), plane_rows = std::min(slab_rows + band, n_rows);
-    if ((rc = ensure(ctx, ctx->ws_ld_member, (size_t)words * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_ld_planes, (size_t)plane_rows * 3 * (size_t)words * sizeof(uint32_t)))) return rc;
-    if (counts && (rc = ensure(ctx, ctx->ws_ld_counts, (size_t)slab_rows * (size_t)band * 9 * sizeof(int32_t)))) return rc;
-    if (r2 && (rc = ensure(ctx, ctx->ws_ld_r2, (size_t)slab_rows * (size_t)band * sizeof(double)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows, band))) return rc;
-    uint32_t *d_planes = (uint32_t *)ctx->ws_ld_planes.p;
-    int32_t *d_counts = counts ? (int32_t *)ctx->ws_ld_counts.p : nullptr;
-    double *d_r2 = r2 ? (double *)ctx->ws_ld_r2.p : nullptr;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_ld_member.p, ordered.data(), (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // membership words; planes [slab rows + band][3][words]; counts and r2 of a slab; row list with its halo
+    uint32_t *d_member, *d_planes;
+    int32_t *d_counts = nullptr;
+    double *d_r2 = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_member, (size_t)words);
+    sc.want(d_planes, (size_t)plane_rows * 3 * (size_t)words);
+    if (counts) sc.want(d_counts, (size_t)slab_rows * (size_t)band * 9);
+    if (r2) sc.want(d_r2, (size_t)slab_rows * (size_t)band);
+    if (row_idx) sc.want(d_rowlist, (size_t)plane_rows);
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d_member, ordered.data(), (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     const bool wide = site_wide_rows(p->d, p->kpitch, p->desc);      // every panel the library makes, except split rows with a tail below 16 bytes
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         const int64_t n_plane = std::min(n_valid + band, n_rows - s0);      // the slab's rows and its halo, as far as the selection goes
         {
             ProfScope ps(ctx, PK_LD_P);
@@ -59,7 +62,7 @@ try {
             const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ctx->n_cu * 16)));
 #define SNPM_LD_LAUNCH(PK, WD)                                                                                                    \
     hipLaunchKernelGGL((k_ld_planes<PK, WD>), grid, dim3(LD_PLANE_THREADS), 0, ctx->stream, (const int8_t *)p->d, p->kpitch, p->desc, p->n_acc, \
-                       d_rows, first, n_plane, (const uint32_t *)ctx->ws_ld_member.p, (int)words, d_planes)
+                       d_rows, first, n_plane, (const uint32_t *)d_member, (int)words, d_planes)
             if (p->packed) { if (wide) SNPM_LD_LAUNCH(true, true); else SNPM_LD_LAUNCH(true, false); }
             else { if (wide) SNPM_LD_LAUNCH(false, true); else SNPM_LD_LAUNCH(false, false); }
 #undef SNPM_LD_LAUNCH

@@ -46,20 +46,21 @@ try {
     const int64_t all_steps = (n_rows + MIX_STEP_ROWS - 1) / MIX_STEP_ROWS;
     std::vector<unsigned long long> masks((size_t)(all_steps * mask_words));        // (lives until the stream is synchronised)
     mix_fill_masks(alt, ref, n_rows, bits, masks.data());
-    if ((rc = ensure(ctx, ctx->ws_mix_planes, (size_t)slab_steps * (size_t)mix_step_bytes(cols_pad)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mix_masks, masks.size() * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mix_out, 8 * cells * sizeof(int32_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_mix_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_mix_cols.p : nullptr;
-    int32_t *d_out = (int32_t *)ctx->ws_mix_out.p;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_mix_planes.p;
-    const unsigned long long *d_masks = (const unsigned long long *)ctx->ws_mix_masks.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_mix_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_mix_masks.p, masks.data(), masks.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // bit-planes [4][cols_pad][W] of a slab; bit slices of the read counts of all rows; the table [2][2][2][ncols][ncols]; column list; row list
+    unsigned long long *d_planes, *d_masks;
+    int32_t *d_out, *d_cols = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_planes, (size_t)slab_steps * (size_t)mix_step_bytes(cols_pad) / 8);
+    sc.want(d_masks, masks.size());
+    sc.want(d_out, 8 * cells);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_masks, masks.data(), masks.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_out, 0, 8 * cells * sizeof(int32_t), ctx->stream));
     // the sums accumulate on the device across slabs
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         const int64_t W = (n_valid + MIX_STEP_ROWS - 1) / MIX_STEP_ROWS * MIX_STEP_WORDS;    // words per plane row of this slab
         {
             ProfScope ps(ctx, PK_WIN_P);

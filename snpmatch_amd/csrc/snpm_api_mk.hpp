@@ -62,33 +62,32 @@ int snpm_panel_marker_select(snpm_panel *panel, const int32_t *cols, int64_t nco
     int rc = wait_upload(p);
     if (rc) return rc;
     const int64_t n_best = (n_rows + MK_GAIN_ROWS - 1) / MK_GAIN_ROWS;
-    if ((rc = ensure(ctx, ctx->ws_mk_planes, (size_t)n_rows * 2 * (size_t)Wc * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_ut, (size_t)Wc * (size_t)cols_pad * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_need, cells))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_gain, (size_t)n_rows * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_best, (size_t)n_best * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_elig, (size_t)n_rows))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_chosen, (size_t)cap * (sizeof(int64_t) + sizeof(int32_t))))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mk_state, sizeof(MkState)))) return rc;
-    if (coord && (rc = ensure(ctx, ctx->ws_mk_coord, (size_t)n_rows * sizeof(int64_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_mk_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if (row_idx && (rc = ensure(ctx, ctx->ws_rows, (size_t)n_rows * sizeof(int64_t)))) return rc;
+    Scratch sc;     // row planes [n_rows][2][Wc]; Ut [Wc][cols_pad]; need; gains; block keys; eligibility; chosen | gain_at; MkState; coordinates; column list; row list
+    unsigned long long *d_H, *d_Ut, *d_best;
+    uint8_t *d_need, *d_elig, *d_picks;
+    int32_t *d_gain, *d_cols = nullptr;
+    MkState *d_st;
+    int64_t *d_coord = nullptr, *d_rows = nullptr;
+    sc.want(d_H, (size_t)n_rows * 2 * (size_t)Wc);
+    sc.want(d_Ut, (size_t)Wc * (size_t)cols_pad);
+    sc.want(d_need, cells);
+    sc.want(d_gain, (size_t)n_rows);
+    sc.want(d_best, (size_t)n_best);
+    sc.want(d_elig, (size_t)n_rows);
+    sc.want(d_picks, (size_t)cap * (sizeof(int64_t) + sizeof(int32_t)));
+    sc.want(d_st, 1);
+    if (coord) sc.want(d_coord, (size_t)n_rows);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rows, (size_t)n_rows);
+    if ((rc = scratch_commit(ctx, sc))) return rc;
     if ((rc = ensure_pinned(ctx, 2 * sizeof(MkState)))) return rc;
     MkState *h_init = (MkState *)ctx->h_pinned, *h_st = h_init + 1;  // what goes up before the first launch; what comes back between batches
     *h_init = init;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_mk_cols.p : nullptr;
-    const int64_t *d_rows = row_idx ? (const int64_t *)ctx->ws_rows.p : nullptr;
-    const int64_t *d_coord = coord ? (const int64_t *)ctx->ws_mk_coord.p : nullptr;
-    unsigned long long *d_H = (unsigned long long *)ctx->ws_mk_planes.p, *d_Ut = (unsigned long long *)ctx->ws_mk_ut.p;
-    unsigned long long *d_best = (unsigned long long *)ctx->ws_mk_best.p;
-    uint8_t *d_need = (uint8_t *)ctx->ws_mk_need.p, *d_elig = (uint8_t *)ctx->ws_mk_elig.p;
-    int32_t *d_gain = (int32_t *)ctx->ws_mk_gain.p;
-    int64_t *d_chosen = (int64_t *)ctx->ws_mk_chosen.p;
+    int64_t *d_chosen = (int64_t *)d_picks;
     int32_t *d_gain_at = (int32_t *)(d_chosen + cap);
-    MkState *d_st = (MkState *)ctx->ws_mk_state.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_mk_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (row_idx) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_rows.p, row_idx, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (coord) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_mk_coord.p, coord, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (row_idx) HIPCHK(ctx, hipMemcpyAsync(d_rows, row_idx, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (coord) HIPCHK(ctx, hipMemcpyAsync(d_coord, coord, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     if (eligible) HIPCHK(ctx, hipMemcpyAsync(d_elig, eligible, (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
     else HIPCHK(ctx, hipMemsetAsync(d_elig, 1, (size_t)n_rows, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_st, h_init, sizeof(MkState), hipMemcpyHostToDevice, ctx->stream));

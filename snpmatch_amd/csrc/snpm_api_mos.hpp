@@ -72,19 +72,20 @@ try {
         top_cls = std::max(top_cls, s.group * s.W * 3);
         top_cc = std::max(top_cc, s.group * (s.ch_hi - s.ch_lo));
     }
-    if ((rc = ensure(ctx, ctx->ws_mos_planes, (size_t)(4 * cols_pad * top.W) * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mos_sw, (size_t)top_sw * (size_t)cols_pad * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mos_j, (size_t)top_rows_g * 2 * sizeof(int32_t)))) return rc;              // j | state
-    if ((rc = ensure(ctx, ctx->ws_mos_cls, (size_t)top_cls * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mos_chains, (size_t)top_chains * MOS_CHAIN_WORDS * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_mos_out, (size_t)top_cc * (size_t)(1 + (col_cost ? ncols : 0)) * sizeof(int32_t)))) return rc;     // chain_cost | col_cost
-    if (cols && (rc = ensure(ctx, ctx->ws_mos_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, top.n_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_mos_cols.p : nullptr;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_mos_planes.p, *d_sw = (unsigned long long *)ctx->ws_mos_sw.p;
-    unsigned long long *d_cls = (unsigned long long *)ctx->ws_mos_cls.p;
-    int64_t *d_chains = (int64_t *)ctx->ws_mos_chains.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_mos_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;     // bit-planes [4][cols_pad][W] of a slab of whole chains; sw words, j | state and class words of a group of samples; chain table; chain_cost | col_cost; column list; row list
+    unsigned long long *d_planes, *d_sw, *d_cls;
+    int32_t *d_j, *d_cost, *d_cols = nullptr;
+    int64_t *d_chains, *d_rowlist = nullptr;
+    sc.want(d_planes, (size_t)(4 * cols_pad * top.W));
+    sc.want(d_sw, (size_t)top_sw * (size_t)cols_pad);
+    sc.want(d_j, (size_t)top_rows_g * 2);
+    sc.want(d_cls, (size_t)top_cls);
+    sc.want(d_chains, (size_t)top_chains * MOS_CHAIN_WORDS);
+    sc.want(d_cost, (size_t)top_cc * (size_t)(1 + (col_cost ? ncols : 0)));
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(top.n_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     std::vector<int64_t> h_chains;
     std::vector<unsigned long long> h_cls;
     for (const MosSlab &s : slabs) {
@@ -100,7 +101,7 @@ try {
         }
         HIPCHK(ctx, hipMemcpyAsync(d_chains, h_chains.data(), h_chains.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         // the planes of the slab's rows: the shared walk, over this slab alone
-        rc = for_each_row_slab(ctx, row_idx ? row_idx + s.r0 : nullptr, row0 + s.r0, s.n_rows, s.n_rows,
+        rc = for_each_row_slab(ctx, row_idx ? row_idx + s.r0 : nullptr, d_rowlist, row0 + s.r0, s.n_rows, s.n_rows,
                                [&](const int64_t *d_rows, int64_t first, int64_t, int64_t n_valid) {
             ProfScope ps(ctx, PK_WIN_P);
             const dim3 grid((unsigned)s.W, (unsigned)(cols_pad / WN_PL_COLS));
@@ -112,8 +113,7 @@ try {
         if (rc) return rc;
         for (int64_t g0 = 0; g0 < n_samples; g0 += s.group) {
             const int64_t g = std::min(s.group, n_samples - g0);
-            int32_t *d_j = (int32_t *)ctx->ws_mos_j.p, *d_state = d_j + g * s.n_rows;
-            int32_t *d_cost = (int32_t *)ctx->ws_mos_out.p, *d_cc = col_cost ? d_cost + g * n_ch : nullptr;
+            int32_t *d_state = d_j + g * s.n_rows, *d_cc = col_cost ? d_cost + g * n_ch : nullptr;
             h_cls.assign((size_t)(g * s.W * 3), 0ull);
             for (int64_t i = 0; i < g; ++i) {
                 const uint8_t *c = sample_class + (g0 + i) * n_rows + s.r0;

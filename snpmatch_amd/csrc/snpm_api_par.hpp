@@ -46,27 +46,26 @@ try {
     const int n_tiles = (int)((ncols + F1X_TILE - 1) / F1X_TILE);
     const size_t grp_bytes = plan.groups.size() * sizeof(int64_t), off_bytes = plan.step_off.size() * sizeof(int64_t);
     const size_t seg_bytes = plan.segs.size() * sizeof(unsigned long long);
-    if ((rc = ensure(ctx, ctx->ws_par_planes, (size_t)F1X_PLANES * (size_t)cols_pad * (size_t)plan.max_W * 8))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_par_groups, grp_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_par_steps, off_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_par_segs, seg_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_par_out, 4 * cells * sizeof(int32_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_par_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if (row_idx && (rc = ensure(ctx, ctx->ws_rows, (size_t)plan.max_rows * sizeof(int64_t)))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_par_cols.p : nullptr;
-    const int64_t *d_rows = row_idx ? (const int64_t *)ctx->ws_rows.p : nullptr;
-    int32_t *d_out = (int32_t *)ctx->ws_par_out.p;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_par_planes.p;
-    const int64_t *d_groups = (const int64_t *)ctx->ws_par_groups.p, *d_steps = (const int64_t *)ctx->ws_par_steps.p;
-    const unsigned long long *d_segs = (const unsigned long long *)ctx->ws_par_segs.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_par_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_par_groups.p, plan.groups.data(), grp_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_par_steps.p, plan.step_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_par_segs.p, plan.segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // bit-planes [4][cols_pad][W] of a slab; group table; step offsets; segments; score | n_tot | w_first | w_het; column list; row list
+    unsigned long long *d_planes, *d_segs;
+    int64_t *d_groups, *d_steps, *d_rows = nullptr;
+    int32_t *d_out, *d_cols = nullptr;
+    sc.want(d_planes, (size_t)F1X_PLANES * (size_t)cols_pad * (size_t)plan.max_W);
+    sc.want(d_groups, plan.groups.size());
+    sc.want(d_steps, plan.step_off.size());
+    sc.want(d_segs, plan.segs.size());
+    sc.want(d_out, 4 * cells);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rows, (size_t)plan.max_rows);
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_groups, plan.groups.data(), grp_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_steps, plan.step_off.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_segs, plan.segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_out, 0, 4 * cells * sizeof(int32_t), ctx->stream));
     for (const ParSlab &s : plan.slabs) {
         // (stream order: the previous slab's plane kernel has read its rows before this copy lands)
-        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_rows.p, row_idx + s.r0, (size_t)s.n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(d_rows, row_idx + s.r0, (size_t)s.n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         {
             ProfScope ps(ctx, PK_WIN_P);
             const dim3 grid((unsigned)s.W, (unsigned)(cols_pad / F1X_PL_COLS));

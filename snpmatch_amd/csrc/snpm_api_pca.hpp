@@ -48,18 +48,21 @@ try {
     const int n_tiles = (int)(cols_pad / PCA_TILE), n_pairs = n_tiles * (n_tiles + 1) / 2, splits = pca_gram_splits(n_pairs);
     const int64_t slab_steps = pca_slab_steps(ctx->pca_ws_bytes, cols_pad, n_rows), slab_rows = slab_steps * PCA_STEP_ROWS;
     const size_t plane_bytes = (size_t)slab_steps * (size_t)(4 * cols_pad * PCA_STEP_WORDS * 8);
-    if ((rc = ensure(ctx, ctx->ws_pca_planes, plane_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_pca_tab, (size_t)std::min(slab_rows, n_rows) * 4 * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_pca_part, (size_t)splits * (size_t)n_pairs * PCA_TILE * PCA_TILE * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_pca_out, cells * sizeof(double)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_pca_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_pca_cols.p : nullptr;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_pca_planes.p;
-    double *d_tab = (double *)ctx->ws_pca_tab.p, *d_part = (double *)ctx->ws_pca_part.p, *d_gram = (double *)ctx->ws_pca_out.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_pca_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // bit-planes [4][cols_pad][W] and table rows of a slab; partials [splits][tile pairs][64][64]; the matrix; column list; row list
+    unsigned long long *d_planes;
+    double *d_tab, *d_part, *d_gram;
+    int32_t *d_cols = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_planes, plane_bytes / 8);
+    sc.want(d_tab, (size_t)std::min(slab_rows, n_rows) * 4);
+    sc.want(d_part, (size_t)splits * (size_t)n_pairs * PCA_TILE * PCA_TILE);
+    sc.want(d_gram, cells);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_gram, 0, cells * sizeof(double), ctx->stream));
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         const int64_t W = (n_valid + PCA_STEP_ROWS - 1) / PCA_STEP_ROWS * PCA_STEP_WORDS;    // words per plane row of this slab
         // (stream order: the previous slab's k_pca_gram has read its table rows before this copy lands)
         HIPCHK(ctx, hipMemcpyAsync(d_tab, tab + 4 * s0, (size_t)n_valid * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -116,19 +119,22 @@ try {
     int rc = wait_upload(p);
     if (rc) return rc;
     const int64_t slab_rows = pca_load_slab_rows(ctx->pca_ws_bytes, k, n_rows);
-    if ((rc = ensure(ctx, ctx->ws_pca_tab, (size_t)slab_rows * 4 * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_pca_load, (size_t)slab_rows * (size_t)k * sizeof(double)))) return rc;
     const int kp = pca_load_pitch(k);                                // vec rows padded with zeros to whole groups of components
-    if ((rc = ensure(ctx, ctx->ws_pca_vec, (size_t)ncols * (size_t)kp * sizeof(double)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_pca_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_pca_cols.p : nullptr;
-    double *d_tab = (double *)ctx->ws_pca_tab.p, *d_load = (double *)ctx->ws_pca_load.p, *d_vec = (double *)ctx->ws_pca_vec.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_pca_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // table rows and loadings of a slab; vec [ncols][kp]; column list; row list
+    double *d_tab, *d_load, *d_vec;
+    int32_t *d_cols = nullptr;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_tab, (size_t)slab_rows * 4);
+    sc.want(d_load, (size_t)slab_rows * (size_t)k);
+    sc.want(d_vec, (size_t)ncols * (size_t)kp);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if (kp != k) HIPCHK(ctx, hipMemsetAsync(d_vec, 0, (size_t)ncols * (size_t)kp * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipMemcpy2DAsync(d_vec, (size_t)kp * sizeof(double), vec, (size_t)k * sizeof(double), (size_t)k * sizeof(double), (size_t)ncols,
                                  hipMemcpyHostToDevice, ctx->stream));
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         HIPCHK(ctx, hipMemcpyAsync(d_tab, tab + 4 * s0, (size_t)n_valid * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         {
             ProfScope ps(ctx, PK_PCA_L);

@@ -1,4 +1,4 @@
-// snpm_api_rows.hpp -- what the table calls (pairsnp, genotype_cross, its HMM) and the panel scans (kinship, site statistics, LD) share on the host: the check of an offset table, of a row's genotype codes, of a row selection, and the walk over row slabs (inside the anonymous namespace of snpm_api.hip).
+// snpm_api_rows.hpp -- what the table calls (pairsnp, genotype_cross, its HMM) and the panel scans (kinship, site statistics, LD) share on the host: the check of an offset table, of a row's genotype codes, of a row selection, the scratch of a scan and the walk over row slabs (inside the anonymous namespace of snpm_api.hip).
 // Part of the one translation unit of libsnpmatch_hip.so: included by snpm_api.hip at this place, not on its own.
 // Every check only reads host memory and reports through set_err: a caller runs it before the device is touched.
 
@@ -31,25 +31,28 @@ int check_rows(snpm_ctx *ctx, const snpm_panel *p, const int64_t *row_idx, int64
     return SNPM_OK;
 }
 
-// The selected rows, `slab_rows` at a time: body(d_rows, first, s0, n_valid) queues the work of slab rows [s0, s0 + n_valid), whose
-// row k is panel row d_rows[first + k], or first + k for a range (d_rows null).  A row list travels slab by slab into ws_rows
-// (stream order: the previous slab's kernel has read its part before this copy lands); ensure_slab_rows sizes that buffer for
-// ONE slab, where the caller sizes its other workspaces.  The caller's row_idx is read until the stream is synchronised.
-// halo: rows BEHIND a slab that its work reads as well (the band of snpm_panel_ld_band): the list of a slab then holds up to
-// n_valid + halo rows, as far as the selection goes.
-int ensure_slab_rows(snpm_ctx *ctx, const int64_t *row_idx, int64_t slab_rows, int64_t n_rows, int64_t halo = 0)
+// The device scratch of one panel scan (snpm_scratch.hpp): all parts of `s` in ctx->ws_scan, which grows to the largest call.
+int scratch_commit(snpm_ctx *ctx, Scratch &s)
 {
-    return row_idx ? ensure(ctx, ctx->ws_rows, (size_t)std::min(slab_rows + halo, n_rows) * sizeof(int64_t)) : SNPM_OK;
+    if (!s.ok()) return set_err(ctx, SNPM_ERR_OOM, "the device scratch of this call does not fit the address space");
+    if (int rc = ensure(ctx, ctx->ws_scan, s.total())) return rc;
+    s.assign(ctx->ws_scan.p);
+    return SNPM_OK;
 }
 
+// The selected rows, `slab_rows` at a time: body(d_rows, first, s0, n_valid) queues the work of slab rows [s0, s0 + n_valid), whose
+// row k is panel row d_rows[first + k], or first + k for a range (d_rows null).  A row list travels slab by slab into `d_rows`, the
+// caller's scratch part of min(slab_rows + halo, n_rows) entries, null without a list (stream order: the previous slab's kernel
+// has read its part before this copy lands).  The caller's row_idx is read until the stream is synchronised.
+// halo: rows BEHIND a slab that its work reads as well (the band of snpm_panel_ld_band): the list of a slab then holds up to
+// n_valid + halo rows, as far as the selection goes.
 template <class Body>
-int for_each_row_slab(snpm_ctx *ctx, const int64_t *row_idx, int64_t row0, int64_t n_rows, int64_t slab_rows, Body body, int64_t halo = 0)
+int for_each_row_slab(snpm_ctx *ctx, const int64_t *row_idx, int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t slab_rows, Body body, int64_t halo = 0)
 {
-    const int64_t *d_rows = row_idx ? (const int64_t *)ctx->ws_rows.p : nullptr;
     for (int64_t s0 = 0; s0 < n_rows; s0 += slab_rows) {
         const int64_t n_valid = std::min(slab_rows, n_rows - s0);
-        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_rows.p, row_idx + s0, (size_t)std::min(n_valid + halo, n_rows - s0) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-        if (int rc = body(d_rows, row_idx ? (int64_t)0 : row0 + s0, s0, n_valid)) return rc;
+        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(d_rows, row_idx + s0, (size_t)std::min(n_valid + halo, n_rows - s0) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = body(row_idx ? d_rows : nullptr, row_idx ? (int64_t)0 : row0 + s0, s0, n_valid)) return rc;
     }
     return SNPM_OK;
 }

@@ -44,21 +44,23 @@ try {
     // slabs of the row axis: whole LDS steps of the seven planes inside the workspace budget (sim_slab_steps of snpm_k_sim.hpp)
     const int64_t slab_steps = sim_slab_steps(ctx->sim_ws_bytes, cols_pad, n_rows), slab_rows = slab_steps * F1X_STEP_ROWS;
     const size_t slab_plane_words = (size_t)cols_pad * (size_t)slab_steps * F1X_STEP_WORDS;      // words of one plane of a full slab
-    if ((rc = ensure(ctx, ctx->ws_sim_planes, (size_t)slab_steps * (size_t)sim_step_bytes(cols_pad)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_sim_grp, (size_t)(n_grp + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_sim_out, 2 * cells * sizeof(int32_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_sim_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_sim_cols.p : nullptr;
-    const int64_t *d_grp = (const int64_t *)ctx->ws_sim_grp.p;
-    int32_t *d_score = (int32_t *)ctx->ws_sim_out.p, *d_ninfo = d_score + cells;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_sim_planes.p;
+    Scratch sc;                                                      // bit-planes [4 + 3][cols_pad][W] of a slab; grp_off; score | ninfo; column list; row list
+    unsigned long long *d_planes;
+    int64_t *d_grp, *d_rowlist = nullptr;
+    int32_t *d_score, *d_cols = nullptr;
+    sc.want(d_planes, (size_t)slab_steps * (size_t)sim_step_bytes(cols_pad) / 8);
+    sc.want(d_grp, (size_t)(n_grp + 1));
+    sc.want(d_score, 2 * cells);
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    int32_t *d_ninfo = d_score + cells;
     unsigned long long *d_q = d_planes + F1X_PLANES * slab_plane_words;          // (behind the P planes of the LARGEST slab)
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_sim_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_sim_grp.p, grp_off, (size_t)(n_grp + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_grp, grp_off, (size_t)(n_grp + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_score, 0, 2 * cells * sizeof(int32_t), ctx->stream));
     // the results accumulate on the device across slabs
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         const int64_t W = (n_valid + F1X_STEP_ROWS - 1) / F1X_STEP_ROWS * F1X_STEP_WORDS;    // words per plane row of this slab
         {
             ProfScope ps(ctx, PK_WIN_P);

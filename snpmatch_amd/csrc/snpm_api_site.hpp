@@ -53,21 +53,25 @@ try {
     int rc = wait_upload(p);
     if (rc) return rc;
     const int64_t slab_rows = site_slab_rows(ctx->site_ws_bytes, n_groups, n_rows);
-    if ((rc = ensure(ctx, ctx->ws_site_out, (size_t)n_groups * (size_t)slab_rows * 16))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_site_member, member.size() * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure_slab_rows(ctx, row_idx, slab_rows, n_rows))) return rc;
-    int32_t *d_out = (int32_t *)ctx->ws_site_out.p;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_site_member.p, member.data(), member.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                       // counts [groups][slab rows][4]; membership bitmasks [groups][words]; row list
+    int32_t *d_out;
+    uint32_t *d_member;
+    int64_t *d_rowlist = nullptr;
+    sc.want(d_out, (size_t)n_groups * (size_t)slab_rows * 4);
+    sc.want(d_member, member.size());
+    if (row_idx) sc.want(d_rowlist, (size_t)std::min(slab_rows, n_rows));
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d_member, member.data(), member.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     const int rpw = WAVE >> lg_s, waves = SITE_THREADS / WAVE;
     const bool wide = site_wide_rows(p->d, p->kpitch, p->desc);      // every panel the library makes, except split rows with a tail below 16 bytes
-    rc = for_each_row_slab(ctx, row_idx, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
+    rc = for_each_row_slab(ctx, row_idx, d_rowlist, row0, n_rows, slab_rows, [&](const int64_t *d_rows, int64_t first, int64_t s0, int64_t n_valid) {
         {
             ProfScope ps(ctx, PK_SITE);
             const int64_t batches = (n_valid + rpw - 1) / rpw;
             const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((batches + waves - 1) / waves, (int64_t)ctx->n_cu * 2)));
 #define SNPM_SITE_LAUNCH(PK, WD)                                                                                                  \
     hipLaunchKernelGGL((k_site_counts<PK, WD>), grid, dim3(SITE_THREADS), 0, ctx->stream, (const int8_t *)p->d, p->kpitch, p->desc, p->n_acc, \
-                       d_rows, first, n_valid, (const uint32_t *)ctx->ws_site_member.p, (int)n_groups, lg_s, cpl, d_out)
+                       d_rows, first, n_valid, (const uint32_t *)d_member, (int)n_groups, lg_s, cpl, d_out)
             if (p->packed) { if (wide) SNPM_SITE_LAUNCH(true, true); else SNPM_SITE_LAUNCH(true, false); }
             else { if (wide) SNPM_SITE_LAUNCH(false, true); else SNPM_SITE_LAUNCH(false, false); }
 #undef SNPM_SITE_LAUNCH

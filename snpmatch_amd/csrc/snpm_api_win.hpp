@@ -51,29 +51,30 @@ try {
         max_rows = std::max(max_rows, std::min(steps * WN_STEP_ROWS, n_rows - s0));
         s0 += steps * WN_STEP_ROWS;
     }
-    if ((rc = ensure(ctx, ctx->ws_win_planes, (size_t)max_steps * (size_t)win_step_bytes(cols_pad)))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_win_cells, (size_t)max_w * (size_t)cell_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->ws_win_off, (size_t)(n_win + 1) * sizeof(int64_t)))) return rc;
-    if (cols && (rc = ensure(ctx, ctx->ws_win_cols, (size_t)ncols * sizeof(int32_t)))) return rc;
-    if (pairs && (rc = ensure(ctx, ctx->ws_win_pairs, 2 * (size_t)pairs * sizeof(int32_t)))) return rc;
-    if (row_idx && (rc = ensure(ctx, ctx->ws_rows, (size_t)max_rows * sizeof(int64_t)))) return rc;
-    const int32_t *d_cols = cols ? (const int32_t *)ctx->ws_win_cols.p : nullptr;
-    const int32_t *d_pa = pairs ? (const int32_t *)ctx->ws_win_pairs.p : nullptr, *d_pb = pairs ? d_pa + pairs : nullptr;
-    const int64_t *d_rows = row_idx ? (const int64_t *)ctx->ws_rows.p : nullptr;
-    unsigned long long *d_planes = (unsigned long long *)ctx->ws_win_planes.p;
-    int32_t *d_cells = (int32_t *)ctx->ws_win_cells.p;
-    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_win_cols.p, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    Scratch sc;                                                      // bit-planes [4][cols_pad][W] and cells of a slab; win_off; column list; pa | pb; row list
+    unsigned long long *d_planes;
+    int32_t *d_cells, *d_cols = nullptr, *d_pa = nullptr;
+    int64_t *d_off, *d_rows = nullptr;
+    sc.want(d_planes, (size_t)max_steps * (size_t)win_step_bytes(cols_pad) / 8);
+    sc.want(d_cells, (size_t)max_w * (size_t)cell_bytes / 4);
+    sc.want(d_off, (size_t)(n_win + 1));
+    if (cols) sc.want(d_cols, (size_t)ncols);
+    if (pairs) sc.want(d_pa, 2 * (size_t)pairs);
+    if (row_idx) sc.want(d_rows, (size_t)max_rows);
+    if ((rc = scratch_commit(ctx, sc))) return rc;
+    int32_t *d_pb = pairs ? d_pa + pairs : nullptr;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(d_cols, cols, (size_t)ncols * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if (pairs) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->ws_win_pairs.p, pair_a, (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync((int32_t *)ctx->ws_win_pairs.p + pairs, pair_b, (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_pa, pair_a, (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_pb, pair_b, (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ws_win_off.p, win_off, (size_t)(n_win + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_off, win_off, (size_t)(n_win + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     std::vector<int32_t> host_cells((size_t)max_w * (size_t)(acc_cols + pairs) * 4);
     for (const Slab &sl : slabs) {
         const int64_t n_valid = std::min(sl.steps * WN_STEP_ROWS, n_rows - sl.s0);
         const int64_t W = (n_valid + WN_STEP_ROWS - 1) / WN_STEP_ROWS * WN_STEP_WORDS;     // words per plane row of this slab
         // (a row list travels slab by slab; the previous slab's stream was synchronised, so its rows are no longer read)
-        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(ctx->ws_rows.p, row_idx + sl.s0, (size_t)n_valid * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        if (row_idx) HIPCHK(ctx, hipMemcpyAsync(d_rows, row_idx + sl.s0, (size_t)n_valid * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         {
             ProfScope ps(ctx, PK_WIN_P);
             const dim3 grid((unsigned)W, (unsigned)(cols_pad / WN_PL_COLS));
@@ -88,7 +89,7 @@ try {
             const int64_t per_block = WN_THREADS >> lg, blocks = (items + per_block - 1) / per_block;
             const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ctx->n_cu * 64)));
             hipLaunchKernelGGL(k_win_count, grid, dim3(WN_THREADS), 0, ctx->stream, (const unsigned long long *)d_planes, cols_pad, W, sl.s0, n_valid,
-                               (const int64_t *)ctx->ws_win_off.p, sl.w_lo, sl.n_w, acc_cols, d_pa, d_pb, pairs, lg, d_cells);
+                               (const int64_t *)d_off, sl.w_lo, sl.n_w, acc_cols, d_pa, d_pb, pairs, lg, d_cells);
             HIPCHK(ctx, hipGetLastError());
         }
         HIPCHK(ctx, hipMemcpyAsync(host_cells.data(), d_cells, (size_t)items * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
